@@ -24,6 +24,12 @@ barrier + torch.cuda.synchronize on both sides (the load generator holds at
 a WARM/GO handshake over stdin so the brackets are real); elapsed = MAX
 over ranks; rank 0 prints one JSON line; value = whole-job req/s across all
 N GPUs.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. --dump-outputs DIR additionally writes
+what the timed path returned in its LAST timed step (see write_outputs).
+--full is reserved for secondary measurements that need runs of their own;
+the benchmark has none today, so it changes nothing yet.
 """
 
 from __future__ import annotations
@@ -33,6 +39,7 @@ import asyncio
 import json
 import os
 import random
+import re
 import statistics
 import sys
 import tempfile
@@ -71,6 +78,64 @@ def make_request(rng: random.Random, tool_names: List[str], rid: int, flagged_fr
         {"jsonrpc": "2.0", "id": rid, "method": "tools/call", "params": {"name": name, "arguments": args}},
         separators=(",", ":"),
     ).encode()
+
+
+DUMP_MAX_ROWS = 8192   # responses kept (the first rows of the corpus / last batch)
+DUMP_WIDTH = 1024      # bytes kept per response body (zero padded / truncated)
+_WALL_CLOCK = re.compile(rb"\d{4}-\d{2}-\d{2}T\d{2}:\d{2}:\d{2}Z")
+
+
+def write_outputs(dump_dir: str, requests: List[bytes], statuses: List[int],
+                  bodies: List[bytes]) -> None:
+    """--dump-outputs: what a caller of the timed path received in the last
+    timed step, row i answering requests[i] (inputs are seeded, so row i is
+    the same request in every run with the same arguments).
+
+      response_status.npy  float32 [n]        HTTP status (200 in engine mode);
+                                              0 = request i was not sent in the last step
+      response_length.npy  float32 [n]        full body length in bytes
+      response_bytes.npy   float32 [n, 1024]  body bytes, zero padded / truncated
+
+    n = min(len(requests), 8192): a fixed prefix, 32 MiB at the most. The one
+    value that differs between two runs by design, the wall clock that
+    get_system_time returns, is zeroed so runs compare byte for byte.
+    """
+    import numpy as np
+
+    n = min(len(requests), DUMP_MAX_ROWS)
+    status = np.zeros(n, dtype=np.float32)
+    length = np.zeros(n, dtype=np.float32)
+    mat = np.zeros((n, DUMP_WIDTH), dtype=np.float32)
+    for i in range(n):
+        body = bytes(bodies[i])
+        if b'get_system_time"' in requests[i]:
+            body = _WALL_CLOCK.sub(b"0000-00-00T00:00:00Z", body)
+        status[i] = statuses[i]
+        length[i] = len(body)
+        row = np.frombuffer(body[:DUMP_WIDTH], dtype=np.uint8)
+        mat[i, :row.shape[0]] = row
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "response_status.npy"), status)
+    np.save(os.path.join(dump_dir, "response_length.npy"), length)
+    np.save(os.path.join(dump_dir, "response_bytes.npy"), mat)
+
+
+def read_hey_dump(path: str, n: int):
+    """Parse forge_hey's --dump-file: per payload int32 status, uint32
+    length, body bytes, in corpus order."""
+    import struct
+
+    statuses, bodies = [], []
+    with open(path, "rb") as f:
+        blob = f.read()
+    off = 0
+    for _ in range(n):
+        st, ln = struct.unpack_from("<iI", blob, off)
+        off += 8
+        statuses.append(st)
+        bodies.append(blob[off:off + ln])
+        off += ln
+    return statuses, bodies
 
 
 def local_tool_names(rank: int, upstreams: int) -> List[str]:
@@ -195,11 +260,14 @@ async def run_http(args, rank: int, world: int, use_gpu: bool, R: int):
     # are uniform over ALL ranks' tools so world>1 drives the RCCL fan-out
     all_names = [n for r in range(world) for n in local_tool_names(r, args.upstreams)]
     rng = random.Random(1000003 * (rank + 1))
+    corpus = [make_request(rng, all_names, i, args.flagged_frac, args.payload_bytes,
+                           args.unknown_frac, args.nonascii_frac) for i in range(args.payloads)]
     with tempfile.NamedTemporaryFile("wb", suffix=".jsonl", delete=False) as f:
         payload_file = f.name
-        for i in range(args.payloads):
-            f.write(make_request(rng, all_names, i, args.flagged_frac, args.payload_bytes,
-                                 args.unknown_frac, args.nonascii_frac) + b"\n")
+        for req in corpus:
+            f.write(req + b"\n")
+    # only rank 0 dumps: the generator keeps the last timed step's responses
+    dump_file = payload_file + ".responses" if (args.dump_outputs and rank == 0) else None
 
     hey_threads = max(2, min(6, (os.cpu_count() or 16) // (2 * max(world, 1))))
     proc = await asyncio.create_subprocess_exec(
@@ -208,6 +276,7 @@ async def run_http(args, rank: int, world: int, use_gpu: bool, R: int):
         "--requests-per-step", str(R), "--warmup", str(args.warmup),
         "--steps", str(args.steps), "--payload-file", payload_file,
         "--auth", f"Bearer {token}",
+        *(["--dump-file", dump_file] if dump_file else []),
         stdin=asyncio.subprocess.PIPE, stdout=asyncio.subprocess.PIPE)
 
     line = await proc.stdout.readline()  # warmup steps run now
@@ -222,6 +291,10 @@ async def run_http(args, rank: int, world: int, use_gpu: bool, R: int):
     await sync(collectives, use_gpu)     # closing bracket
     elapsed_here = time.monotonic() - t_start
     os.unlink(payload_file)
+    if dump_file:
+        statuses, bodies = read_hey_dump(dump_file, len(corpus))
+        os.unlink(dump_file)
+        write_outputs(args.dump_outputs, corpus, statuses, bodies)
 
     elapsed = max_over_ranks(res["elapsed_s"], world, use_gpu)
     all_res = gather_objects(res, world)
@@ -322,9 +395,9 @@ async def run_engine_only(args, rank: int, world: int, use_gpu: bool, R: int):
         if conc > 1:
             k = (len(step_data[s]) + conc - 1) // conc
             parts = [step_data[s][i:i + k] for i in range(0, len(step_data[s]), k)]
-            await asyncio.gather(*(engine.process_rpc_batch(p) for p in parts))
+            last_parts = await asyncio.gather(*(engine.process_rpc_batch(p) for p in parts))
         else:
-            await engine.process_rpc_batch(step_data[s])
+            last_out = await engine.process_rpc_batch(step_data[s])
         if use_gpu:
             torch.cuda.synchronize()
         step_times.append(time.monotonic() - t0)
@@ -333,6 +406,10 @@ async def run_engine_only(args, rank: int, world: int, use_gpu: bool, R: int):
         prof.dump_stats(os.environ["FORGE_CPROFILE"])
     await sync(collectives, use_gpu)
     elapsed = max_over_ranks(time.monotonic() - t_start, world, use_gpu)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        if conc > 1:
+            last_out = [o for part in last_parts for o in part]
+        write_outputs(args.dump_outputs, step_data[-1], [200] * len(last_out), last_out)
 
     if rank == 0:
         value = R * args.steps * world / elapsed
@@ -400,6 +477,11 @@ async def main() -> None:
                     help="allowlist the bench tools in the semantic cache (labeled in output)")
     ap.add_argument("--no-gpu", action="store_true")
     ap.add_argument("--engine-only", action="store_true", help="alias for --mode engine")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's responses as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run secondary measurements that take runs of their own "
+                         "(none today: the headline run is all this benchmark does)")
     args = ap.parse_args()
     if args.engine_only:
         args.mode = "engine"

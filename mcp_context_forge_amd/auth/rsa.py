@@ -168,7 +168,12 @@ class JWKSet:
         """Synchronous JWKS fetch with TTL (verification is sync)."""
         import time as _t
 
-        if not self.url or _t.monotonic() - self._fetched_at < self.cache_ttl_s:
+        if not self.url:
+            return
+        # _fetched_at == 0.0 means "never fetched / forced refresh": the
+        # monotonic clock's origin is arbitrary (often boot), so 0.0 must not
+        # be read as a timestamp or a young clock would look like a warm cache
+        if self._fetched_at and _t.monotonic() - self._fetched_at < self.cache_ttl_s:
             return
         import httpx
 

@@ -13,6 +13,10 @@
 //   * run K timed steps of R requests each; per-step wall time measured
 //     here; per-request latencies recorded during timed steps only
 //   * print one JSON line with totals + latency percentiles, exit 0
+//   * with --dump-file PATH: during the LAST timed step keep, per payload
+//     index, the status + body of the last response received for it, and
+//     write them to PATH after the run (int32 status, uint32 length, body
+//     bytes per payload, in corpus order; status 0 = not sent in that step)
 //
 // Each connection is closed-loop: send request, read full response, send
 // the next. A step ends when R requests have completed; connections idle
@@ -66,6 +70,7 @@ struct Config {
     std::vector<std::string> payloads;  // rotated round-robin
     std::string auth;                   // Authorization header value
     bool handshake = true;              // WARM/GO coordination
+    std::string dump_file;              // last-step responses (empty = off)
 };
 
 struct Conn {
@@ -95,6 +100,9 @@ struct Shared {
     std::mutex mu;
     std::condition_variable cv;
     long step_target = 0;
+    // --dump-file only
+    std::atomic<bool> capture{false}; // keep response bodies (last timed step)
+    std::atomic<long> cap_next{0};    // shared payload rotation of the capture step
 };
 
 int connect_to(const Config& c) {
@@ -124,6 +132,9 @@ std::string build_request(const Config& c, const std::string& payload) {
     return o.str();
 }
 
+// kDump = --dump-file given. A compile-time switch, so that a plain run
+// executes the request loop without the capture bookkeeping.
+template <bool kDump>
 struct Worker {
     Shared* sh;
     const Config* cfg;
@@ -133,12 +144,23 @@ struct Worker {
     std::vector<std::string> reqs;  // prebuilt request bytes, rotated
     size_t req_idx = 0;
     std::vector<uint32_t> local_lat;
+    std::vector<std::string> cap_body;  // per payload index (kDump only)
+    std::vector<int> cap_status;
+    std::vector<size_t> conn_sent;      // per connection: payload index in flight
+    std::vector<int> conn_status;       // per connection: status being read
 
     void start_one(Conn& c, int idx) {
         long rem = sh->remaining.fetch_sub(1);
         if (rem <= 0) {
             sh->remaining.fetch_add(1);
             return;
+        }
+        // capture step: one shared rotation, so payloads 0..R-1 (mod P) are
+        // all sent whatever share of the step each thread ends up serving
+        if constexpr (kDump) {
+            if (sh->capture.load(std::memory_order_relaxed))
+                req_idx = (size_t)sh->cap_next.fetch_add(1) % reqs.size();
+            conn_sent[(size_t)idx] = req_idx;
         }
         c.out = reqs[req_idx];
         req_idx = (req_idx + 1) % reqs.size();
@@ -235,6 +257,7 @@ struct Worker {
             int status = 0;
             if (c.in.size() > 12) status = atoi(c.in.data() + 9);
             if (status != 200 && status != 202) sh->non200++;
+            if constexpr (kDump) conn_status[(size_t)idx] = status;
             // content-length
             size_t cl = 0;
             const char* h = c.in.data();
@@ -257,6 +280,13 @@ struct Worker {
         double lat = mono_s() - c.t_send;
         if (sh->record.load(std::memory_order_relaxed))
             local_lat.push_back((uint32_t)(lat * 1e6));
+        if constexpr (kDump) {
+            if (sh->capture.load(std::memory_order_relaxed)) {
+                size_t p = conn_sent[(size_t)idx];
+                cap_body[p].assign(c.in.data() + c.header_len, c.need);
+                cap_status[p] = conn_status[(size_t)idx];
+            }
+        }
         c.busy = false;
         sh->inflight--;
         c.in.erase(0, c.header_len + c.need);
@@ -290,6 +320,12 @@ struct Worker {
         for (size_t i = 0; i < cfg->payloads.size(); ++i)
             reqs.push_back(build_request(*cfg, cfg->payloads[i]));
         req_idx = (size_t)tid % reqs.size();
+        if constexpr (kDump) {
+            cap_body.resize(reqs.size());
+            cap_status.assign(reqs.size(), 0);
+            conn_sent.assign((size_t)per, 0);
+            conn_status.assign((size_t)per, 0);
+        }
 
         int last_phase = 0;
         struct epoll_event evs[128];
@@ -335,6 +371,9 @@ double pct(std::vector<uint32_t>& v, double p) {
     return (double)v[k] / 1000.0;  // ms
 }
 
+template <bool kDump>
+int drive(Config& cfg);
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -355,6 +394,7 @@ int main(int argc, char** argv) {
         else if (a == "--payload-file") payload_file = next();
         else if (a == "--auth") cfg.auth = next();
         else if (a == "--no-handshake") cfg.handshake = false;
+        else if (a == "--dump-file") cfg.dump_file = next();
         else {
             fprintf(stderr, "unknown arg %s\n", a.c_str());
             return 2;
@@ -371,13 +411,20 @@ int main(int argc, char** argv) {
             "{\"jsonrpc\":\"2.0\",\"id\":1,\"method\":\"ping\"}");
     if (cfg.threads < 1) cfg.threads = 1;
     if (cfg.connections < cfg.threads) cfg.connections = cfg.threads;
+    return cfg.dump_file.empty() ? drive<false>(cfg) : drive<true>(cfg);
+}
 
+namespace {
+
+// connect, run the warmup and timed steps, report
+template <bool kDump>
+int drive(Config& cfg) {
     Shared sh;
     sh.cfg = &cfg;
-    std::vector<std::unique_ptr<Worker>> workers;
+    std::vector<std::unique_ptr<Worker<kDump>>> workers;
     std::vector<std::thread> threads;
     for (int t = 0; t < cfg.threads; ++t) {
-        auto w = std::make_unique<Worker>();
+        auto w = std::make_unique<Worker<kDump>>();
         w->sh = &sh;
         w->cfg = &cfg;
         w->tid = t;
@@ -409,10 +456,36 @@ int main(int argc, char** argv) {
     }
     std::vector<double> step_s;
     double t0 = mono_s();
-    for (int s = 0; s < cfg.steps; ++s) step_s.push_back(run_step(true));
+    for (int s = 0; s < cfg.steps; ++s) {
+        if (kDump && s == cfg.steps - 1) sh.capture = true;
+        step_s.push_back(run_step(true));
+    }
     double elapsed = mono_s() - t0;
     sh.phase = -1;
     for (auto& th : threads) th.join();
+
+    if (kDump) {
+        FILE* df = fopen(cfg.dump_file.c_str(), "wb");
+        if (df == nullptr) {
+            fprintf(stderr, "cannot write %s\n", cfg.dump_file.c_str());
+            return 4;
+        }
+        for (size_t i = 0; i < cfg.payloads.size(); ++i) {
+            int32_t status = 0;
+            const std::string* body = nullptr;
+            for (auto& w : workers)  // lowest thread id that saw payload i
+                if (i < w->cap_status.size() && w->cap_status[i] != 0) {
+                    status = w->cap_status[i];
+                    body = &w->cap_body[i];
+                    break;
+                }
+            uint32_t len = body ? (uint32_t)body->size() : 0;
+            fwrite(&status, sizeof(status), 1, df);
+            fwrite(&len, sizeof(len), 1, df);
+            if (len) fwrite(body->data(), 1, len, df);
+        }
+        fclose(df);
+    }
 
     long total = (long)cfg.steps * cfg.requests_per_step;
     double p50 = pct(sh.lat_us, 0.50), p90 = pct(sh.lat_us, 0.90), p99 = pct(sh.lat_us, 0.99);
@@ -426,3 +499,5 @@ int main(int argc, char** argv) {
     fflush(stdout);
     return 0;
 }
+
+}  // namespace

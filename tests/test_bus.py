@@ -4,6 +4,9 @@ forwarding over Redis — tests the exchange-pump request/response semantics).""
 import os
 import subprocess
 import sys
+from pathlib import Path
+
+REPO = str(Path(__file__).resolve().parent.parent)
 
 WORKER = r"""
 import asyncio, json, sys
@@ -50,10 +53,10 @@ dist.destroy_process_group()
 def test_bus_gloo_world2(tmp_path):
     script = tmp_path / "bus_worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, PYTHONPATH="/root/repo")
+    env = dict(os.environ, PYTHONPATH=REPO)
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29651", str(script)],
-        capture_output=True, text=True, timeout=240, env=env, cwd="/root/repo")
+        capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "BUS_OK" in out.stdout

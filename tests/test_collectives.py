@@ -7,6 +7,9 @@ import json
 import os
 import subprocess
 import sys
+from pathlib import Path
+
+REPO = str(Path(__file__).resolve().parent.parent)
 
 WORKER = r"""
 import json, os, sys
@@ -60,24 +63,24 @@ dist.destroy_process_group()
 def test_collectives_gloo_world2(tmp_path):
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", PYTHONPATH="/root/repo")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", PYTHONPATH=REPO)
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29611", str(script)],
-        capture_output=True, text=True, timeout=240, env=env, cwd="/root/repo")
+        capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "COLLECTIVES_OK" in out.stdout
 
 
 def test_bench_cpu_world2_smoke():
     """The bench's sharded step over gloo world 2 (CPU fallback path)."""
-    env = dict(os.environ, PYTHONPATH="/root/repo")
+    env = dict(os.environ, PYTHONPATH=REPO)
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29613", "bench.py",
          "--no-gpu", "--steps", "2", "--warmup", "1", "--requests-per-step", "32",
          "--upstreams", "4"],
-        capture_output=True, text=True, timeout=300, env=env, cwd="/root/repo")
+        capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

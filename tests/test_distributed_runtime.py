@@ -5,6 +5,9 @@ replacement — reference: session_affinity + plugin invalidation pub/sub)."""
 import os
 import subprocess
 import sys
+from pathlib import Path
+
+REPO = str(Path(__file__).resolve().parent.parent)
 
 WORKER = r"""
 import asyncio, json, os, sys
@@ -66,11 +69,11 @@ def test_distributed_runtime_world2(tmp_path):
     script = tmp_path / "dist_worker.py"
     script.write_text(WORKER)
     db = tmp_path / "shared.db"
-    env = dict(os.environ, PYTHONPATH="/root/repo", SHARED_DB=str(db))
+    env = dict(os.environ, PYTHONPATH=REPO, SHARED_DB=str(db))
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29671", str(script)],
-        capture_output=True, text=True, timeout=240, env=env, cwd="/root/repo")
+        capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "DISTRIBUTED_OK" in out.stdout
 
@@ -138,10 +141,10 @@ def test_cross_rank_tool_routing_world2(tmp_path):
     the rpc_batch bus handler both directions)."""
     script = tmp_path / "router_worker.py"
     script.write_text(ROUTER_WORKER)
-    env = dict(os.environ, PYTHONPATH="/root/repo")
+    env = dict(os.environ, PYTHONPATH=REPO)
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29673", str(script)],
-        capture_output=True, text=True, timeout=240, env=env, cwd="/root/repo")
+        capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "ROUTING_OK" in out.stdout

@@ -17,9 +17,12 @@ import json
 import os
 import subprocess
 import sys
+from pathlib import Path
 
 import pytest
 import torch
+
+REPO = str(Path(__file__).resolve().parent.parent)
 
 pytestmark = pytest.mark.gpu
 
@@ -100,7 +103,7 @@ def test_world2_fabric_on_gpu(tmp_path):
         pytest.skip("no ROCm device")
     script = tmp_path / "rccl_worker.py"
     script.write_text(WORKER)
-    env = dict(os.environ, PYTHONPATH="/root/repo")
+    env = dict(os.environ, PYTHONPATH=REPO)
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", "29677", str(script)],

@@ -14,8 +14,8 @@ from pathlib import Path
 
 import pytest
 
-CSRC = Path("/root/repo/mcp_context_forge_amd/ops/csrc")
-BUILD = Path("/root/repo/mcp_context_forge_amd/ops")
+BUILD = Path(__file__).resolve().parent.parent / "mcp_context_forge_amd" / "ops"
+CSRC = BUILD / "csrc"
 SOURCES = ["envelope.cpp", "upstream.cpp", "fastpath.cpp", "rewrite.cpp", "pool.cpp", "san_driver.cpp"]
 
 

@@ -5,12 +5,15 @@ import asyncio
 import json
 import subprocess
 import sys
+from pathlib import Path
 
 import pytest
 
+REPO = str(Path(__file__).resolve().parent.parent)
+
 STDIO_ENV = {"DATABASE_URL": "sqlite://", "FORGE_FEDERATION_ENABLED": "false",
              "FORGE_AUTH_REQUIRED": "false", "FORGE_PLUGINS_ENABLED": "false",
-             "PYTHONPATH": "/root/repo"}
+             "PYTHONPATH": REPO}
 
 
 def test_stdio_server_subprocess():
@@ -18,7 +21,7 @@ def test_stdio_server_subprocess():
 
     env = dict(os.environ, **STDIO_ENV)
     proc = subprocess.Popen([sys.executable, "-m", "mcp_context_forge_amd", "stdio"],
-                            stdin=subprocess.PIPE, stdout=subprocess.PIPE, env=env, cwd="/root/repo")
+                            stdin=subprocess.PIPE, stdout=subprocess.PIPE, env=env, cwd=REPO)
     try:
         def rpc(obj):
             proc.stdin.write(json.dumps(obj).encode() + b"\n")
@@ -74,10 +77,10 @@ def test_stdio_subprocess_manager_and_translate_app(run):
 def test_cli_token_mint():
     import os
 
-    env = dict(os.environ, PYTHONPATH="/root/repo")
+    env = dict(os.environ, PYTHONPATH=REPO)
     out = subprocess.run([sys.executable, "-m", "mcp_context_forge_amd", "token",
                           "--user", "x@y.com", "--admin"],
-                         capture_output=True, text=True, env=env, cwd="/root/repo", timeout=60)
+                         capture_output=True, text=True, env=env, cwd=REPO, timeout=60)
     assert out.returncode == 0
     token = out.stdout.strip()
     from mcp_context_forge_amd.auth import jwt as jwt_mod
@@ -94,7 +97,7 @@ def test_plugin_scaffold_cli(tmp_path):
     import subprocess
     import sys
 
-    env = {"PYTHONPATH": "/root/repo", "PATH": "/usr/bin:/bin"}
+    env = {"PYTHONPATH": REPO, "PATH": "/usr/bin:/bin"}
     r = subprocess.run([sys.executable, "-m", "mcp_context_forge_amd", "plugin-scaffold",
                         "my_guard", "--dir", str(tmp_path)],
                        capture_output=True, text=True, env=env, timeout=120)
