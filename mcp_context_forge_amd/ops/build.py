@@ -31,10 +31,8 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     lib_mtime = LIB.stat().st_mtime
-    for f in SOURCES + ["common.h"]:
-        if (CSRC / f).stat().st_mtime > lib_mtime:
-            return True
-    return False
+    watched = [CSRC / f for f in SOURCES] + sorted(CSRC.glob("*.h"))
+    return any(f.stat().st_mtime > lib_mtime for f in watched)
 
 
 def build_pybridge(force: bool = False, verbose: bool = True) -> Path:

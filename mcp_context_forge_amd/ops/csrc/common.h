@@ -5,21 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
-#include <stdio.h>
+
+#include "forge_api.h"
 
 #define WAVE 64  // CDNA wavefront width (hard-coded per guide: warpSize==64 on gfx950)
-
-#define HIP_CHECK(expr)                                                              \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if (_e != hipSuccess) {                                                      \
-            fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(_e),        \
-                    __FILE__, __LINE__);                                             \
-            return (int)_e;                                                          \
-        }                                                                            \
-    } while (0)
-
-typedef __hip_bfloat16 bf16_t;
 
 // 8 x bf16 stored as shorts — the vectorized load unit (guide G13).
 typedef __attribute__((ext_vector_type(8))) short short8;
@@ -49,5 +38,33 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 }
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+template <int ACT>
+__device__ __forceinline__ float apply_act(float v) {
+    if constexpr (ACT == FORGE_ACT_GELU) v = gelu_tanh(v);
+    if constexpr (ACT == FORGE_ACT_SIGMOID) v = sigmoidf(v);
+    return v;
+}
+
+// Sum over the wave; the total is valid in lane 0 (shfl_down by 32..1).
+__device__ __forceinline__ float wave_sum(float v) {
+    #pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
+// One wave's bf16 dot of two K-element rows (K % 8 == 0, 16-byte aligned):
+// lane-strided 8-element chunks accumulated in element order, then wave_sum.
+__device__ __forceinline__ float wave_dot_bf16(const short* __restrict__ a_row,
+                                               const short* __restrict__ b_row, int K, int lane) {
+    float dot = 0.0f;
+    for (int k = lane * 8; k < K; k += WAVE * 8) {
+        short8 av = *(const short8*)(a_row + k);
+        short8 bv = *(const short8*)(b_row + k);
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) dot += bf16_to_f(av[j]) * bf16_to_f(bv[j]);
+    }
+    return wave_sum(dot);
+}
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

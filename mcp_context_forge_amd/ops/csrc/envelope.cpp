@@ -17,7 +17,8 @@
 #include <functional>
 #include <vector>
 
-extern "C" void forge_parallel_for(int n, void (*fn)(int, void*), void* ctx);
+#include "forge_api.h"
+
 namespace {
 inline void run_parallel(int n, const std::function<void(int)>& f) {
     forge_parallel_for(

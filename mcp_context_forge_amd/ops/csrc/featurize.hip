@@ -64,8 +64,7 @@ __global__ __launch_bounds__(256) void featurize_kernel(
         float c = (float)hist[i];
         ss += c * c;
     }
-    #pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) ss += __shfl_down(ss, off);
+    ss = wave_sum(ss);
     __shared__ float wave_ss[8];
     int wid = threadIdx.x / WAVE;
     if ((threadIdx.x & (WAVE - 1)) == 0) wave_ss[wid] = ss;

@@ -17,10 +17,7 @@
 // Preconditions (host wrapper pads): M%128==0, N%128==0, K%64==0,
 // A row-major [M,K] bf16, BT row-major [N,K] bf16, C row-major [M,N].
 
-#include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "gemm_common.h"
 
 #define BM 128
 #define BN 128
@@ -33,7 +30,7 @@ __device__ __forceinline__ uint32_t swz(uint32_t byte_off) {
     return byte_off ^ (((byte_off >> 7) & 7u) << 4);
 }
 
-// ACT: 0 = none, 1 = gelu(tanh), 2 = sigmoid.  OUT_BF16: emit bf16 instead of f32.
+// ACT: a FORGE_ACT_* code.  OUT_BF16: emit bf16 instead of f32.
 template <int ACT, bool OUT_BF16, bool HAS_BIAS>
 __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     const short* __restrict__ A,   // [M,K] bf16 bits
@@ -111,24 +108,14 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
         __syncthreads();
     }
 
-    // ---- epilogue: C/D layout col=lane&15, row=(lane>>4)*4+reg (guide §3, m89/m91) ----
+    // ---- epilogue ----
     #pragma unroll
     for (int m = 0; m < 4; ++m) {
         #pragma unroll
         for (int n = 0; n < 4; ++n) {
             int col = tile_n + wn * 64 + n * 16 + (lane & 15);
-            float b = HAS_BIAS ? bias[col] : 0.0f;
-            #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                int row = tile_m + wm * 64 + m * 16 + (lane >> 4) * 4 + reg;
-                float v = acc[m][n][reg] + b;
-                if constexpr (ACT == 1) v = gelu_tanh(v);
-                if constexpr (ACT == 2) v = sigmoidf(v);
-                if constexpr (OUT_BF16)
-                    ((short*)C)[(size_t)row * N + col] = f_to_bf16(v);
-                else
-                    ((float*)C)[(size_t)row * N + col] = v;
-            }
+            int row0 = tile_m + wm * 64 + m * 16 + (lane >> 4) * 4;
+            store_frag<ACT, OUT_BF16, HAS_BIAS>(acc[m][n], bias, C, N, row0, col);
         }
     }
 }
@@ -137,31 +124,14 @@ extern "C" int forge_gemm_bt(
     const void* A, const void* BT, const void* bias, void* C,
     int M, int N, int K, int act, int out_bf16, void* stream)
 {
-    if ((M % BM) || (N % BN) || (K % BK)) return 9001;
+    if ((M % BM) || (N % BN) || (K % BK)) return FORGE_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(M / BM, N / BN);
-    dim3 block(256);
-    bool hb = bias != nullptr;
-    #define DISPATCH(A_, O_, B_)                                                                  \
-        hipLaunchKernelGGL((gemm_bt_kernel<A_, O_, B_>), grid, block, 0, s,                       \
-                           (const short*)A, (const short*)BT, (const float*)bias, C, M, N, K)
-    switch (act * 4 + (out_bf16 ? 2 : 0) + (hb ? 1 : 0)) {
-        case 0: DISPATCH(0, false, false); break;
-        case 1: DISPATCH(0, false, true); break;
-        case 2: DISPATCH(0, true, false); break;
-        case 3: DISPATCH(0, true, true); break;
-        case 4: DISPATCH(1, false, false); break;
-        case 5: DISPATCH(1, false, true); break;
-        case 6: DISPATCH(1, true, false); break;
-        case 7: DISPATCH(1, true, true); break;
-        case 8: DISPATCH(2, false, false); break;
-        case 9: DISPATCH(2, false, true); break;
-        case 10: DISPATCH(2, true, false); break;
-        case 11: DISPATCH(2, true, true); break;
-        default: return 9002;
-    }
-    #undef DISPATCH
-    return (int)hipGetLastError();
+    return dispatch_epilogue(act, out_bf16 != 0, bias != nullptr, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((gemm_bt_kernel<E::act, E::out_bf16, E::has_bias>), grid, dim3(256), 0, s,
+                           (const short*)A, (const short*)BT, (const float*)bias, C, M, N, K);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -181,22 +151,9 @@ __global__ __launch_bounds__(256) void gemv_head_kernel(
     const short* a_row = A + (size_t)wave_global * K;
 
     for (int c = 0; c < C; ++c) {
-        const short* w_row = WT + (size_t)c * K;
-        float dot = 0.0f;
-        for (int k = lane * 8; k < K; k += WAVE * 8) {
-            short8 av = *(const short8*)(a_row + k);
-            short8 wv = *(const short8*)(w_row + k);
-            #pragma unroll
-            for (int j = 0; j < 8; ++j) dot += bf16_to_f(av[j]) * bf16_to_f(wv[j]);
-        }
-        #pragma unroll
-        for (int off = WAVE / 2; off > 0; off >>= 1) dot += __shfl_down(dot, off);
-        if (lane == 0) {
-            float v = dot + (bias ? bias[c] : 0.0f);
-            if constexpr (ACT == 1) v = gelu_tanh(v);
-            if constexpr (ACT == 2) v = sigmoidf(v);
-            out[(size_t)wave_global * C + c] = v;
-        }
+        float dot = wave_dot_bf16(a_row, WT + (size_t)c * K, K, lane);
+        if (lane == 0)
+            out[(size_t)wave_global * C + c] = apply_act<ACT>(dot + (bias ? bias[c] : 0.0f));
     }
 }
 
@@ -204,16 +161,20 @@ extern "C" int forge_gemv_head(
     const void* A, const void* WT, const void* bias, void* out,
     int M, int C, int K, int act, void* stream)
 {
-    if (K % (WAVE * 8)) return 9003;
+    if (K % (WAVE * 8)) return FORGE_ERR_GEMV_K;
     hipStream_t s = (hipStream_t)stream;
     int waves_per_block = 256 / WAVE;
     int grid = ceil_div(M, waves_per_block);
+    #define LAUNCH_HEAD(ACT_)                                                              \
+        hipLaunchKernelGGL(gemv_head_kernel<ACT_>, dim3(grid), dim3(256), 0, s,            \
+                           (const short*)A, (const short*)WT, (const float*)bias, (float*)out, M, C, K)
     switch (act) {
-        case 0: hipLaunchKernelGGL(gemv_head_kernel<0>, dim3(grid), dim3(256), 0, s, (const short*)A, (const short*)WT, (const float*)bias, (float*)out, M, C, K); break;
-        case 1: hipLaunchKernelGGL(gemv_head_kernel<1>, dim3(grid), dim3(256), 0, s, (const short*)A, (const short*)WT, (const float*)bias, (float*)out, M, C, K); break;
-        case 2: hipLaunchKernelGGL(gemv_head_kernel<2>, dim3(grid), dim3(256), 0, s, (const short*)A, (const short*)WT, (const float*)bias, (float*)out, M, C, K); break;
-        default: return 9002;
+        case FORGE_ACT_NONE: LAUNCH_HEAD(FORGE_ACT_NONE); break;
+        case FORGE_ACT_GELU: LAUNCH_HEAD(FORGE_ACT_GELU); break;
+        case FORGE_ACT_SIGMOID: LAUNCH_HEAD(FORGE_ACT_SIGMOID); break;
+        default: return FORGE_ERR_ACT;
     }
+    #undef LAUNCH_HEAD
     return (int)hipGetLastError();
 }
 

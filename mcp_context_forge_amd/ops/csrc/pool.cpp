@@ -17,6 +17,8 @@
 #include <thread>
 #include <vector>
 
+#include "forge_api.h"
+
 namespace {
 
 struct Task {

@@ -27,55 +27,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" {
-int forge_parse_envelopes(const uint8_t*, const int64_t*, int, int32_t*, int32_t*, int32_t*,
-                          int32_t*, int32_t*, int32_t*, int32_t*);
-void* forge_toolmap_new(const uint8_t*, const int32_t*, const int32_t*, int);
-void forge_toolmap_free(void*);
-void forge_toolmap_resolve(void*, const uint8_t*, const int32_t*, const int32_t*, int, int32_t*);
-void* forge_store_new(int);
-void forge_store_put(void*, int, const uint8_t*, int64_t);
-int64_t forge_store_get(void*, int, uint8_t*, int64_t);
-void forge_store_free(void*);
-void* forge_cache_new(double);
-void forge_cache_free(void*);
-int64_t forge_decide(
-    const uint8_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-    const int32_t*, const int32_t*, const int32_t*,
-    const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
-    const uint32_t*, const uint8_t*, const int32_t*, const float*, const uint8_t*,
-    const int32_t*, const uint64_t*, int,
-    const uint32_t*, const uint32_t*, const uint64_t*,
-    const int32_t*, const int32_t*, const uint8_t*, const int8_t*, uint32_t,
-    const uint8_t*, const int32_t*, int, const uint8_t*, const int32_t*, int,
-    const uint8_t*, const int32_t*, int,
-    void*, void*, double,
-    int32_t*, int32_t*, int8_t*, uint8_t*, int64_t, int64_t*, int64_t*);
-int64_t forge_upstream_call_batch(const uint8_t*, const int32_t*, const int32_t*,
-                                  const int32_t*, int, const char*,
-                                  uint8_t*, int64_t, int64_t*, int64_t*);
-int64_t forge_rewrite_rows(const uint8_t*, const int32_t*, const int32_t*, int,
-                           const uint8_t*, const uint32_t*, uint32_t, int, int, int,
-                           const uint8_t*, const int32_t*, int, int,
-                           int32_t*, uint32_t*, int32_t*, uint8_t*, int64_t,
-                           int64_t*, int64_t*, int64_t*, int64_t*,
-                           const uint8_t*, const int32_t*, int, int32_t*,
-                           const uint8_t*, const int32_t*, const int32_t*,
-                           const int8_t*, const uint8_t*,
-                           const int32_t*, const int32_t*, uint8_t*);
-int64_t forge_post_rows(const uint8_t*, const int64_t*, const int64_t*, int,
-                        const uint8_t*, uint32_t, int,
-                        const uint8_t*, const int32_t*, int, int64_t, double,
-                        int32_t*, uint32_t*, int32_t*, uint8_t*,
-                        uint8_t*, int64_t, int64_t*, int64_t*);
-int64_t forge_finalize(
-    const uint8_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-    const int32_t*, const uint64_t*, int, const int32_t*, int,
-    const uint8_t*, const int64_t*, const int64_t*, const uint8_t*,
-    const int32_t*, const int32_t*, const uint8_t*, const uint32_t*,
-    void*, double, double,
-    uint8_t*, int64_t, int64_t*, int64_t*, uint8_t*, uint8_t*);
-}
+#include "forge_api.h"
 
 namespace {
 

@@ -14,6 +14,31 @@
 
 #include "common.h"
 
+#include <stddef.h>
+
+struct ScanTables {
+    const uint16_t* next;    // [S, C]
+    const uint8_t* klass;    // [256]
+    const uint32_t* accept;  // [S]
+};
+
+// Block-cooperative copy of one bank's tables into LDS; returns the LDS
+// copies. The layout (next, klass, accept back to back) is what
+// FORGE_SCAN_TABLE_BYTES sizes. Every thread of the block must call it.
+__device__ __forceinline__ ScanTables stage_tables_lds(
+    uint8_t* lds_raw, const ScanTables& g, int n_states, int n_classes)
+{
+    uint16_t* lnext = (uint16_t*)lds_raw;
+    uint8_t* lklass = (uint8_t*)(lds_raw + (size_t)n_states * n_classes * 2);
+    uint32_t* laccept = (uint32_t*)(lklass + 256);
+    int total16 = n_states * n_classes;
+    for (int i = threadIdx.x; i < total16; i += blockDim.x) lnext[i] = g.next[i];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) lklass[i] = g.klass[i];
+    for (int i = threadIdx.x; i < n_states; i += blockDim.x) laccept[i] = g.accept[i];
+    __syncthreads();
+    return ScanTables{lnext, lklass, laccept};
+}
+
 template <bool USE_LDS>
 __global__ __launch_bounds__(256) void scan_kernel(
     const uint8_t* __restrict__ data,     // packed bytes
@@ -28,21 +53,8 @@ __global__ __launch_bounds__(256) void scan_kernel(
     int32_t* __restrict__ out_first_end)  // [B] first match end (or -1); optional
 {
     extern __shared__ uint8_t lds_raw[];
-    const uint16_t* tnext = next;
-    const uint8_t* tklass = klass;
-    const uint32_t* taccept = accept;
-
-    if constexpr (USE_LDS) {
-        uint16_t* lnext = (uint16_t*)lds_raw;
-        uint8_t* lklass = (uint8_t*)(lds_raw + (size_t)n_states * n_classes * 2);
-        uint32_t* laccept = (uint32_t*)(lklass + 256);
-        int total16 = n_states * n_classes;
-        for (int i = threadIdx.x; i < total16; i += blockDim.x) lnext[i] = next[i];
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) lklass[i] = klass[i];
-        for (int i = threadIdx.x; i < n_states; i += blockDim.x) laccept[i] = accept[i];
-        __syncthreads();
-        tnext = lnext; tklass = lklass; taccept = laccept;
-    }
+    ScanTables t{next, klass, accept};
+    if constexpr (USE_LDS) t = stage_tables_lds(lds_raw, t, n_states, n_classes);
 
     int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= batch) return;
@@ -52,8 +64,8 @@ __global__ __launch_bounds__(256) void scan_kernel(
     uint32_t state = 0;
     for (int32_t p = rbeg; p < rend; ++p) {
         uint8_t b = data[p];
-        state = tnext[state * n_classes + tklass[b]];
-        uint32_t a = taccept[state];
+        state = t.next[state * n_classes + t.klass[b]];
+        uint32_t a = t.accept[state];
         if (a) {
             if (first_end < 0) first_end = p + 1 - rbeg;
             mask |= a;
@@ -83,8 +95,15 @@ struct ScanBankDesc {
     int n_states;
     int n_classes;
     int use_lds;   // table fits the dynamic LDS allocation
-    int _pad[2];
+    int _pad[3];
 };
+// ops/hip.py ScanBankSet packs each descriptor as six little-endian int64:
+// [next, klass, accept, n_states | n_classes << 32, use_lds, 0].
+static_assert(sizeof(ScanBankDesc) == 6 * sizeof(int64_t), "ScanBankDesc is six int64");
+static_assert(offsetof(ScanBankDesc, next) == 0 && offsetof(ScanBankDesc, klass) == 8 &&
+              offsetof(ScanBankDesc, accept) == 16 && offsetof(ScanBankDesc, n_states) == 24 &&
+              offsetof(ScanBankDesc, n_classes) == 28 && offsetof(ScanBankDesc, use_lds) == 32,
+              "ScanBankDesc field offsets must match ScanBankSet's packing");
 
 __global__ __launch_bounds__(256) void scan_multi_kernel(
     const uint8_t* __restrict__ data,
@@ -96,20 +115,8 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(
 {
     extern __shared__ uint8_t lds_raw[];
     const ScanBankDesc d = descs[blockIdx.y];
-    const uint16_t* tnext = d.next;
-    const uint8_t* tklass = d.klass;
-    const uint32_t* taccept = d.accept;
-    if (d.use_lds) {
-        uint16_t* lnext = (uint16_t*)lds_raw;
-        uint8_t* lklass = (uint8_t*)(lds_raw + (size_t)d.n_states * d.n_classes * 2);
-        uint32_t* laccept = (uint32_t*)(lklass + 256);
-        int total16 = d.n_states * d.n_classes;
-        for (int i = threadIdx.x; i < total16; i += blockDim.x) lnext[i] = d.next[i];
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) lklass[i] = d.klass[i];
-        for (int i = threadIdx.x; i < d.n_states; i += blockDim.x) laccept[i] = d.accept[i];
-        __syncthreads();
-        tnext = lnext; tklass = lklass; taccept = laccept;
-    }
+    ScanTables t{d.next, d.klass, d.accept};
+    if (d.use_lds) t = stage_tables_lds(lds_raw, t, d.n_states, d.n_classes);
     int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= batch) return;
     int32_t rbeg = beg[r], rend = end_[r];
@@ -117,8 +124,8 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(
     uint32_t state = 0;
     int nc = d.n_classes;
     for (int32_t p = rbeg; p < rend; ++p) {
-        state = tnext[state * nc + tklass[data[p]]];
-        mask |= taccept[state];
+        state = t.next[state * nc + t.klass[data[p]]];
+        mask |= t.accept[state];
     }
     out_mask[(size_t)blockIdx.y * batch + r] = mask;
 }
@@ -146,8 +153,8 @@ extern "C" int forge_scan(
     hipStream_t s = (hipStream_t)stream;
     int block = 256;
     int grid = ceil_div(batch, block);
-    size_t table_bytes = (size_t)n_states * n_classes * 2 + 256 + (size_t)n_states * 4;
-    if (table_bytes <= 64 * 1024) {
+    size_t table_bytes = (size_t)FORGE_SCAN_TABLE_BYTES(n_states, n_classes);
+    if (table_bytes <= FORGE_SCAN_LDS_LIMIT) {
         hipLaunchKernelGGL((scan_kernel<true>), dim3(grid), dim3(block), table_bytes, s,
                            (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                            (const uint16_t*)next, (const uint8_t*)klass, (const uint32_t*)accept,

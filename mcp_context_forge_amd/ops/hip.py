@@ -9,6 +9,7 @@ failure raises, never a silent eager fallback (per the build contract).
 from __future__ import annotations
 
 import ctypes
+import os
 from functools import lru_cache
 from typing import List, Optional, Tuple
 
@@ -22,6 +23,48 @@ class ForgeHipError(RuntimeError):
     pass
 
 
+_KINDS = {"p": ctypes.c_void_p, "s": ctypes.c_char_p, "i": ctypes.c_int, "u": ctypes.c_uint32,
+          "l": ctypes.c_int64, "d": ctypes.c_double, "v": None}
+
+
+def _sig(ret: str, args: str):
+    return _KINDS[ret], [_KINDS[c] for c in args.replace(" ", "")]
+
+
+# name → (restype, argtypes) for EVERY export of csrc/forge_api.h, grouped like
+# its declarations: p pointer, s C string, i int, u uint32, l int64, d double,
+# v void. tests/test_forge_abi.py checks this table against the header.
+_API = {
+    "forge_scan": _sig("i", "ppp i ppp ii pp p"),
+    "forge_scan_multi": _sig("i", "ppp i p ii p p"),
+    "forge_featurize": _sig("i", "ppp ii pp p"),
+    "forge_json_guard": _sig("i", "ppp i ii pp p"),
+    "forge_gemm_bt": _sig("i", "pppp iii ii p"),
+    "forge_gemm_bt_v2": _sig("i", "pppp iii ii p"),
+    "forge_gemv_head": _sig("i", "pppp iii i p"),
+    "forge_rows_argmax_merge": _sig("i", "p iii p pp p"),
+    "forge_rows_gather_scatter_bf16": _sig("i", "ppp p p ii p"),
+    "forge_verify_dot": _sig("i", "ppp p ii p"),
+    "forge_parallel_for": _sig("v", "i p p"),
+    "forge_parse_envelopes": _sig("i", "pp i p pp pp pp"),
+    "forge_upstream_call_batch": _sig("l", "ppp p i s p l pp"),
+    "forge_store_new": _sig("p", "i"),
+    "forge_store_put": _sig("v", "p i p l"),
+    "forge_store_put_batch": _sig("v", "p p i p pp"),
+    "forge_store_get": _sig("l", "p i p l"),
+    "forge_store_free": _sig("v", "p"),
+    "forge_cache_new": _sig("p", "d"),
+    "forge_cache_free": _sig("v", "p"),
+    "forge_toolmap_new": _sig("p", "ppp i"),
+    "forge_toolmap_free": _sig("v", "p"),
+    "forge_toolmap_resolve": _sig("v", "p p pp i p"),
+    "forge_decide": _sig("l", "p pp pp p pp pppppp ppp pp p i ppp ppp p u ppi ppi ppi pp d ppp pl pp"),
+    "forge_finalize": _sig("l", "p pp pp p p i pi ppp p ppp p p dd pl pp pp"),
+    "forge_rewrite_rows": _sig("l", "ppp i pp u i ii pp ii ppp pl pp pp pp i p ppp pp pp p"),
+    "forge_post_rows": _sig("l", "ppp i p u i pp i l d pppp pl pp"),
+}
+
+
 @lru_cache(maxsize=1)
 def _load() -> ctypes.CDLL:
     from .build import LIB, build
@@ -29,41 +72,10 @@ def _load() -> ctypes.CDLL:
     if not LIB.exists():
         build()
     lib = ctypes.CDLL(str(LIB))
-    protos = {
-        "forge_scan": [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3,
-        "forge_scan_multi": [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p,
-                                                    ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 2,
-        "forge_featurize": [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3,
-        "forge_json_guard": [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3,
-        "forge_gemm_bt": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p],
-        "forge_gemm_bt_v2": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p],
-        "forge_gemv_head": [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p],
-        "forge_rows_argmax_merge": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-        "forge_rows_scatter_bf16": [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p],
-        "forge_rows_gather_scatter_bf16": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p],
-        "forge_synchronize": [ctypes.c_void_p],
-        "forge_parse_envelopes": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7,
-        "forge_upstream_call_batch": [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],
-        "forge_rewrite_rows": [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 2 +
-                              [ctypes.c_uint32] + [ctypes.c_int] * 3 +
-                              [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] +
-                              [ctypes.c_void_p] * 3 +
-                              [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 +
-                              [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] +
-                              [ctypes.c_void_p] * 8,
-        "forge_post_rows": [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p] +
-                           [ctypes.c_uint32, ctypes.c_int] +
-                           [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] +
-                           [ctypes.c_int64, ctypes.c_double] +
-                           [ctypes.c_void_p] * 4 +
-                           [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 2,
-    }
-    for name, argtypes in protos.items():
+    for name, (restype, argtypes) in _API.items():
         fn = getattr(lib, name)
+        fn.restype = restype
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name in ("forge_upstream_call_batch",
-                                                "forge_rewrite_rows",
-                                                "forge_post_rows") else ctypes.c_int
     return lib
 
 
@@ -85,6 +97,21 @@ def _check(name: str, rc: int) -> None:
 
 def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _np_ptr(a: Optional[np.ndarray]) -> ctypes.c_void_p:
+    return ctypes.c_void_p(a.ctypes.data) if a is not None else ctypes.c_void_p(0)
+
+
+def _call_growing(cap: int, fn):
+    """Run fn(arena, cap) → bytes used, or -needed when the arena is too
+    small; grow and retry until it fits. → (arena u8[cap], used)."""
+    while True:
+        arena = np.empty(cap, dtype=np.uint8)
+        n = int(fn(arena, cap))
+        if n >= 0:
+            return arena, n
+        cap = -n + 4096
 
 
 class DeviceScanTables:
@@ -114,13 +141,19 @@ def scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, tables: Devic
     return out_mask, out_end
 
 
+# Same pair as FORGE_SCAN_LDS_LIMIT / FORGE_SCAN_TABLE_BYTES in csrc/forge_api.h.
+SCAN_LDS_LIMIT = 64 * 1024
+
+
+def scan_table_bytes(n_states: int, n_classes: int) -> int:
+    return n_states * n_classes * 2 + 256 + n_states * 4
+
+
 class ScanBankSet:
     """Device descriptor table for the fused multi-bank scan
     (scan_multi_kernel): all banks in ONE launch, one [n_banks, B] output.
     Built once per bank combination; holds references to the bank tensors
     so their device memory outlives the descriptor pointers."""
-
-    LDS_LIMIT = 64 * 1024
 
     def __init__(self, banks: List[Tuple[str, "DeviceScanTables"]], device: str = "cuda"):
         self.names = [n for n, _ in banks]
@@ -128,10 +161,11 @@ class ScanBankSet:
         self.n = len(self.banks)
         self.index = {n: i for i, n in enumerate(self.names)}
         self.lds_bytes = 0
+        # one ScanBankDesc (scan.hip, layout static_assert'ed there) per row
         recs = np.zeros((max(self.n, 1), 6), dtype=np.int64)
         for i, b in enumerate(self.banks):
-            tbytes = b.n_states * b.n_classes * 2 + 256 + b.n_states * 4
-            use_lds = 1 if tbytes <= self.LDS_LIMIT else 0
+            tbytes = scan_table_bytes(b.n_states, b.n_classes)
+            use_lds = 1 if tbytes <= SCAN_LDS_LIMIT else 0
             if use_lds:
                 self.lds_bytes = max(self.lds_bytes, tbytes)
             recs[i, 0] = b.next.data_ptr()
@@ -208,9 +242,7 @@ def gemm_bt(a: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = No
     assert k == k2, (a.shape, bt.shape)
     if out is None:
         out = torch.empty((m, n), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=a.device)
-    # v2 (256² tile, 4-phase ring, counted vmcnt) when shapes allow; v1 fallback
-    import os
-
+    # v2 (256² tile, 4-slot ring, counted vmcnt) when shapes allow; v1 otherwise
     if m % 256 == 0 and n % 256 == 0 and k % 32 == 0 and not os.environ.get("FORGE_GEMM_V1"):
         rc = _load().forge_gemm_bt_v2(_ptr(a), _ptr(bt), _ptr(bias), _ptr(out), m, n, k,
                                       act, 1 if out_bf16 else 0, _stream())
@@ -258,11 +290,6 @@ def verify_dot(feats: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor) -> to
     return out
 
 
-def rows_scatter_bf16(src: torch.Tensor, slots: torch.Tensor, dst: torch.Tensor) -> None:
-    r, d = src.shape
-    _check("forge_rows_scatter_bf16", _load().forge_rows_scatter_bf16(_ptr(src), _ptr(slots), _ptr(dst), r, d, _stream()))
-
-
 # ---------------------------------------------------------------------------
 # Host-side native fast path (CPU functions in the same library)
 # ---------------------------------------------------------------------------
@@ -285,9 +312,7 @@ def parse_envelopes(blob: np.ndarray, offsets: np.ndarray) -> dict:
     ar_b = np.empty(n, dtype=np.int32)
     ar_e = np.empty(n, dtype=np.int32)
 
-    def p(a):
-        return ctypes.c_void_p(a.ctypes.data)
-
+    p = _np_ptr
     _check("forge_parse_envelopes", _load().forge_parse_envelopes(
         p(blob), p(offsets), n, p(kind), p(id_b), p(id_e), p(nm_b), p(nm_e), p(ar_b), p(ar_e)))
     return {"kind": kind, "id_beg": id_b, "id_end": id_e,
@@ -301,10 +326,7 @@ def upstream_call_batch(blob: np.ndarray, args_beg: np.ndarray, args_end: np.nda
     res_b = np.empty(n, dtype=np.int64)
     res_e = np.empty(n, dtype=np.int64)
 
-    def p(a):
-        return ctypes.c_void_p(a.ctypes.data)
-
-    lib = _load()
+    lib, p = _load(), _np_ptr
     spans_total = int((args_end[kinds >= 0] - np.maximum(args_beg[kinds >= 0], 0)).clip(min=0).sum()) if n else 0
     cap = spans_total * 3 + n * 256 + 1024
     out = np.empty(cap, dtype=np.uint8)
@@ -321,86 +343,44 @@ def upstream_call_batch(blob: np.ndarray, args_beg: np.ndarray, args_end: np.nda
 # Native decision plane (fastpath.cpp)
 # ---------------------------------------------------------------------------
 
-def _np_ptr(a: Optional[np.ndarray]) -> ctypes.c_void_p:
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else ctypes.c_void_p(0)
-
-
-@lru_cache(maxsize=1)
-def _fastpath_protos() -> ctypes.CDLL:
-    lib = _load()
-    lib.forge_store_new.argtypes = [ctypes.c_int]
-    lib.forge_store_new.restype = ctypes.c_void_p
-    lib.forge_store_put.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
-    lib.forge_store_put.restype = None
-    lib.forge_store_put_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.forge_store_put_batch.restype = None
-    lib.forge_store_free.argtypes = [ctypes.c_void_p]
-    lib.forge_store_free.restype = None
-    lib.forge_cache_new.argtypes = [ctypes.c_double]
-    lib.forge_cache_new.restype = ctypes.c_void_p
-    lib.forge_cache_free.argtypes = [ctypes.c_void_p]
-    lib.forge_cache_free.restype = None
-    lib.forge_toolmap_new.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int]
-    lib.forge_toolmap_new.restype = ctypes.c_void_p
-    lib.forge_toolmap_free.argtypes = [ctypes.c_void_p]
-    lib.forge_toolmap_free.restype = None
-    lib.forge_toolmap_resolve.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]
-    lib.forge_toolmap_resolve.restype = None
-    lib.forge_decide.argtypes = [ctypes.c_void_p] * 20 + [ctypes.c_int] + [ctypes.c_void_p] * 7 + \
-        [ctypes.c_uint32] + \
-        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] * 3 + \
-        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double] + \
-        [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_void_p] * 2
-    lib.forge_store_get.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
-    lib.forge_store_get.restype = ctypes.c_int64
-    lib.forge_decide.restype = ctypes.c_int64
-    lib.forge_finalize.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p, ctypes.c_int] + \
-        [ctypes.c_void_p] * 4 + [ctypes.c_void_p] * 4 + \
-        [ctypes.c_void_p, ctypes.c_double, ctypes.c_double] + \
-        [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
-    lib.forge_finalize.restype = ctypes.c_int64
-    return lib
-
-
 def store_new(capacity: int) -> int:
-    return _fastpath_protos().forge_store_new(capacity)
+    return _load().forge_store_new(capacity)
 
 
 def store_put(store: int, slot: int, data: bytes) -> None:
-    _fastpath_protos().forge_store_put(ctypes.c_void_p(store), slot, data, len(data))
+    _load().forge_store_put(ctypes.c_void_p(store), slot, data, len(data))
 
 
 def store_put_batch(store: int, slots: np.ndarray, blob: np.ndarray,
                     beg: np.ndarray, end: np.ndarray) -> None:
-    _fastpath_protos().forge_store_put_batch(ctypes.c_void_p(store), _np_ptr(slots), slots.shape[0],
+    _load().forge_store_put_batch(ctypes.c_void_p(store), _np_ptr(slots), slots.shape[0],
                                              _np_ptr(blob), _np_ptr(beg), _np_ptr(end))
 
 
 def store_free(store: int) -> None:
-    _fastpath_protos().forge_store_free(ctypes.c_void_p(store))
+    _load().forge_store_free(ctypes.c_void_p(store))
 
 
 def cache_new(ttl: float) -> int:
-    return _fastpath_protos().forge_cache_new(ttl)
+    return _load().forge_cache_new(ttl)
 
 
 def cache_free(cache: int) -> None:
-    _fastpath_protos().forge_cache_free(ctypes.c_void_p(cache))
+    _load().forge_cache_free(ctypes.c_void_p(cache))
 
 
 def toolmap_new(blob: np.ndarray, beg: np.ndarray, end: np.ndarray) -> int:
-    return _fastpath_protos().forge_toolmap_new(_np_ptr(blob), _np_ptr(beg), _np_ptr(end), beg.shape[0])
+    return _load().forge_toolmap_new(_np_ptr(blob), _np_ptr(beg), _np_ptr(end), beg.shape[0])
 
 
 def toolmap_free(tm: int) -> None:
-    _fastpath_protos().forge_toolmap_free(ctypes.c_void_p(tm))
+    _load().forge_toolmap_free(ctypes.c_void_p(tm))
 
 
 def toolmap_resolve(tm: int, blob: np.ndarray, name_beg: np.ndarray, name_end: np.ndarray) -> np.ndarray:
     m = name_beg.shape[0]
     out = np.empty(m, dtype=np.int32)
-    _fastpath_protos().forge_toolmap_resolve(ctypes.c_void_p(tm), _np_ptr(blob),
+    _load().forge_toolmap_resolve(ctypes.c_void_p(tm), _np_ptr(blob),
                                              _np_ptr(name_beg), _np_ptr(name_end), m, _np_ptr(out))
     return out
 
@@ -414,16 +394,15 @@ def decide(blob, id_beg, id_end, args_beg, args_end, tool_idx, name_beg, name_en
            slot_store: int, exact_cache: int, now: float):
     """→ (state i32[m], native_kind i32[m], arena bytes np, resp_beg i64, resp_end i64)."""
     m = id_beg.shape[0]
-    lib = _fastpath_protos()
+    lib = _load()
     state = np.empty(m, dtype=np.int32)
     nk = np.empty(m, dtype=np.int32)
     reason = np.empty(m, dtype=np.int8)
     resp_beg = np.empty(m, dtype=np.int64)
     resp_end = np.empty(m, dtype=np.int64)
-    cap = m * 96 + 4096
-    while True:
-        arena = np.empty(cap, dtype=np.uint8)
-        n = lib.forge_decide(
+
+    def call(arena, cap):
+        return lib.forge_decide(
             _np_ptr(blob), _np_ptr(id_beg), _np_ptr(id_end), _np_ptr(args_beg), _np_ptr(args_end),
             _np_ptr(tool_idx), _np_ptr(name_beg), _np_ptr(name_end),
             _np_ptr(deny_m), _np_ptr(harm_m), _np_ptr(pii_m), _np_ptr(regex_m), _np_ptr(norm_m), _np_ptr(schema_m),
@@ -438,9 +417,9 @@ def decide(blob, id_beg, id_end, args_beg, args_end, tool_idx, name_beg, name_en
             _np_ptr(mod_cats), _np_ptr(mod_off), mod_off.shape[0] - 1,
             ctypes.c_void_p(slot_store), ctypes.c_void_p(exact_cache), now,
             _np_ptr(state), _np_ptr(nk), _np_ptr(reason), _np_ptr(arena), cap, _np_ptr(resp_beg), _np_ptr(resp_end))
-        if n >= 0:
-            return state, nk, reason, arena, resp_beg, resp_end, int(n)
-        cap = -int(n) + 4096
+
+    arena, used = _call_growing(m * 96 + 4096, call)
+    return state, nk, reason, arena, resp_beg, resp_end, used
 
 
 def finalize(blob, id_beg, id_end, args_beg, args_end, tool_idx, user_hash,
@@ -448,16 +427,15 @@ def finalize(blob, id_beg, id_end, args_beg, args_end, tool_idx, user_hash,
              tname_beg, tname_end, tname_blob, tool_flags,
              exact_cache: int, now: float, exact_ttl: float):
     """→ (arena np, resp_beg i64, resp_end i64, is_error u8, cacheable u8)."""
-    lib = _fastpath_protos()
+    lib = _load()
     n_rows = rows.shape[0]
     resp_beg2 = np.empty(n_rows, dtype=np.int64)
     resp_end2 = np.empty(n_rows, dtype=np.int64)
     is_err = np.empty(n_rows, dtype=np.uint8)
     cacheable = np.empty(n_rows, dtype=np.uint8)
-    cap = int(res_blob.shape[0]) + n_rows * 64 + 4096
-    while True:
-        arena = np.empty(cap, dtype=np.uint8)
-        n = lib.forge_finalize(
+
+    def call(arena, cap):
+        return lib.forge_finalize(
             _np_ptr(blob), _np_ptr(id_beg), _np_ptr(id_end), _np_ptr(args_beg), _np_ptr(args_end),
             _np_ptr(tool_idx), _np_ptr(user_hash), id_beg.shape[0],
             _np_ptr(rows), n_rows,
@@ -466,9 +444,9 @@ def finalize(blob, id_beg, id_end, args_beg, args_end, tool_idx, user_hash,
             ctypes.c_void_p(exact_cache), now, exact_ttl,
             _np_ptr(arena), cap, _np_ptr(resp_beg2), _np_ptr(resp_end2),
             _np_ptr(is_err), _np_ptr(cacheable))
-        if n >= 0:
-            return arena, resp_beg2, resp_end2, is_err, cacheable
-        cap = -int(n) + 4096
+
+    arena, _ = _call_growing(int(res_blob.shape[0]) + n_rows * 64 + 4096, call)
+    return arena, resp_beg2, resp_end2, is_err, cacheable
 
 
 RW_DONE, RW_PUNT, RW_BLOCKED, RW_BADJSON, RW_DENY = 0, 1, 2, 3, 4
@@ -509,10 +487,9 @@ def rewrite_rows(blob: np.ndarray, args_beg: np.ndarray, args_end: np.ndarray,
     sk_blob = sk_beg = sk_end = sk_type = sk_req = None
     if sk_tables is not None:
         sk_blob, sk_beg, sk_end, sk_type, sk_req = sk_tables
-    cap = int((args_end - args_beg).sum()) * 2 + n * 32 + 4096
-    while True:
-        arena = np.empty(cap, dtype=np.uint8)
-        rc = lib.forge_rewrite_rows(
+
+    def call(arena, cap):
+        return lib.forge_rewrite_rows(
             _np_ptr(blob), _np_ptr(args_beg), _np_ptr(args_end), n,
             _np_ptr(do_flags), _np_ptr(pii_want),
             ctypes.c_uint32(pii_active_mask), pii_mode,
@@ -525,9 +502,9 @@ def rewrite_rows(blob: np.ndarray, args_beg: np.ndarray, args_end: np.ndarray,
             _np_ptr(sk_blob), _np_ptr(sk_beg), _np_ptr(sk_end),
             _np_ptr(sk_type), _np_ptr(sk_req),
             _np_ptr(sk_lo), _np_ptr(sk_hi), _np_ptr(schema_ok))
-        if rc >= 0:
-            return status, found, deny_hit, harm_hit, schema_ok, arena, out_beg, out_end, scan_beg, scan_end
-        cap = -int(rc) + 4096
+
+    arena, _ = _call_growing(int((args_end - args_beg).sum()) * 2 + n * 32 + 4096, call)
+    return status, found, deny_hit, harm_hit, schema_ok, arena, out_beg, out_end, scan_beg, scan_end
 
 
 def post_rows(res_blob: np.ndarray, res_beg: np.ndarray, res_end: np.ndarray,
@@ -549,10 +526,9 @@ def post_rows(res_blob: np.ndarray, res_beg: np.ndarray, res_end: np.ndarray,
     out_beg = np.empty(n, dtype=np.int64)
     out_end = np.empty(n, dtype=np.int64)
     n_harm = (harm_off.shape[0] - 1) if harm_off is not None else 0
-    cap = int((res_end - res_beg).sum()) * 2 + n * 64 + 4096
-    while True:
-        arena = np.empty(cap, dtype=np.uint8)
-        rc = lib.forge_post_rows(
+
+    def call(arena, cap):
+        return lib.forge_post_rows(
             _np_ptr(res_blob), _np_ptr(res_beg), _np_ptr(res_end), n,
             _np_ptr(do_flags),
             ctypes.c_uint32(pii_active_mask), pii_mode,
@@ -560,9 +536,9 @@ def post_rows(res_blob: np.ndarray, res_beg: np.ndarray, res_end: np.ndarray,
             ctypes.c_int64(toon_min_size), ctypes.c_double(toon_min_savings),
             _np_ptr(status), _np_ptr(found), _np_ptr(harm_hit), _np_ptr(is_err),
             _np_ptr(arena), cap, _np_ptr(out_beg), _np_ptr(out_end))
-        if rc >= 0:
-            return status, found, harm_hit, is_err, arena, out_beg, out_end
-        cap = -int(rc) + 4096
+
+    arena, _ = _call_growing(int((res_end - res_beg).sum()) * 2 + n * 64 + 4096, call)
+    return status, found, harm_hit, is_err, arena, out_beg, out_end
 
 
 TF_REACHABLE, TF_DENY, TF_PII, TF_REGEX, TF_NORM, TF_MOD, TF_HARM = (1 << i for i in range(7))
@@ -571,7 +547,7 @@ ST_DISPATCH_NATIVE, ST_ANSWERED, ST_REWRITE, ST_HOST_SCHEMA, ST_DISPATCH_PY = 0,
 
 
 def store_get(store: int, slot: int) -> Optional[bytes]:
-    lib = _fastpath_protos()
+    lib = _load()
     buf = ctypes.create_string_buffer(4096)
     n = lib.forge_store_get(ctypes.c_void_p(store), slot, buf, 4096)
     if n < 0 or n == 0:

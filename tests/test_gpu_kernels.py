@@ -4,6 +4,7 @@ Every kernel is compared against the plain-Python/torch fp32 oracle of the
 same op (ops/dfa.py, ops/featurize.py, models/classifier.py).
 """
 
+import functools
 import json
 import random
 
@@ -168,17 +169,6 @@ def test_rows_argmax_merge(hip):
 
 
 @requires_gpu
-def test_rows_scatter(hip):
-    src = torch.randn(4, 64).bfloat16().cuda()
-    dst = torch.zeros(10, 64).bfloat16().cuda()
-    slots = torch.tensor([7, 0, 3, 9], dtype=torch.int32).cuda()
-    hip.rows_scatter_bf16(src, slots, dst)
-    torch.cuda.synchronize()
-    for i, s in enumerate([7, 0, 3, 9]):
-        assert torch.equal(dst[s], src[i])
-
-
-@requires_gpu
 def test_gpu_classifier_matches_cpu_model(hip):
     from mcp_context_forge_amd.gpu.classifier import GpuClassifier
     from mcp_context_forge_amd.models.classifier import HashedTextClassifier
@@ -265,6 +255,64 @@ def test_gemm_v2_vs_v1_same_result(hip):
         del os.environ["FORGE_GEMM_V1"]
     torch.cuda.synchronize()
     assert torch.equal(v1, v2) or (v1 - v2).abs().max().item() < 1e-3
+
+
+# (act, out_bf16, bias) epilogue matrix of both GEMM kernels. K=96 gives v2
+# three K-tiles (prologue, one steady iteration with a prefetch, drain);
+# K=128 gives v1 two.
+_EPI_SHAPES = {"v1": (128, 128, 128), "v2": (256, 256, 96)}
+_EPI_ACTS = {"none": "ACT_NONE", "gelu": "ACT_GELU", "sigmoid": "ACT_SIGMOID"}
+
+
+@functools.lru_cache(maxsize=None)
+def _epilogue_case(kernel):
+    """→ (a, bt, bias, refs): bf16 inputs, fp32 bias and the fp32 CPU
+    reference of every (act name, has_bias) from those same inputs."""
+    m, n, k = _EPI_SHAPES[kernel]
+    g = torch.Generator().manual_seed(23 + m + k)
+    a = (torch.randn(m, k, generator=g) * 0.3).bfloat16()
+    bt = (torch.randn(n, k, generator=g) * 0.3).bfloat16()
+    bias = torch.randn(n, generator=g) * 3.0
+    z = a.float() @ bt.float().t()
+    fns = {"none": lambda x: x,
+           "gelu": lambda x: torch.nn.functional.gelu(x, approximate="tanh"),
+           "sigmoid": torch.sigmoid}
+    refs = {(name, hb): fn(z + bias if hb else z) for name, fn in fns.items() for hb in (False, True)}
+    return a, bt, bias, refs
+
+
+def _epilogue_tol(ref, out_bf16):
+    # the bounds of test_gemm_bt_matches_torch (f32) and
+    # test_gemm_bt_fused_bias_gelu_bf16out (bf16)
+    peak = ref.abs().max().item()
+    return 0.05 * (peak + 1) if out_bf16 else 2e-2 * peak
+
+
+@requires_gpu
+@pytest.mark.parametrize("kernel", ["v1", "v2"])
+@pytest.mark.parametrize("act", ["none", "gelu", "sigmoid"])
+@pytest.mark.parametrize("out_bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("has_bias", [False, True], ids=["nobias", "bias"])
+def test_gemm_epilogue_matrix(hip, monkeypatch, kernel, act, out_bf16, has_bias):
+    """Every (act, out dtype, bias) combination of both GEMM kernels lands on
+    its own epilogue instantiation, vs fp32 torch on the CPU."""
+    if kernel == "v1":
+        monkeypatch.setenv("FORGE_GEMM_V1", "1")
+    else:
+        monkeypatch.delenv("FORGE_GEMM_V1", raising=False)
+    a, bt, bias, refs = _epilogue_case(kernel)
+    ref = refs[(act, has_bias)]
+    tol = _epilogue_tol(ref, out_bf16)
+    # no other (act, bias) wiring can pass: each is >= 4 tolerances away
+    for other, wrong in refs.items():
+        if other != (act, has_bias):
+            assert (wrong - ref).abs().max().item() >= 4 * tol, (other, tol)
+    got = hip.gemm_bt(a.cuda(), bt.cuda(), bias.cuda() if has_bias else None,
+                      act=getattr(hip, _EPI_ACTS[act]), out_bf16=out_bf16)
+    assert got.dtype == (torch.bfloat16 if out_bf16 else torch.float32)
+    err = (got.float().cpu() - ref).abs().max().item()
+    print(f"epilogue {kernel} {act} bf16={out_bf16} bias={has_bias}: err {err:.4g} tol {tol:.4g}")
+    assert err < tol, (err, tol)
 
 
 @requires_gpu
@@ -364,6 +412,36 @@ def test_scan_multi_matches_per_bank():
         single, _ = hip.scan(data, beg, end, bank)
         torch.cuda.synchronize()
         assert torch.equal(fused[bs.index[name]], single), name
+
+    # a bank whose tables do not fit LDS (read through L2) next to one that does
+    rng = random.Random(21)
+    words = ["".join(rng.choice("abcdefghijklmnopqrstuvwxyz0123456789") for _ in range(40))
+             for _ in range(32)]
+    big = dfa.compile_literals(words, True)
+    assert hip.scan_table_bytes(big.n_states, big.n_classes) > hip.SCAN_LDS_LIMIT
+    assert big.n_states * big.n_classes * 2 + 256 + big.n_states * 4 > 64 * 1024
+    small = dfa.compile_literals(["forbidden", "blocked_word"], True)
+    assert hip.scan_table_bytes(small.n_states, small.n_classes) <= hip.SCAN_LDS_LIMIT
+    rows = []
+    for i in range(64):
+        w = words[i % 32]
+        rows.append([w.encode(), w.upper().encode() + b" forbidden", w[:39].encode(), b"",
+                     b"x" + w[1:].encode() + words[(i + 5) % 32].encode(), b"Blocked_Word " + w[20:].encode(),
+                     b"plain text", (w + w).encode()][i % 8])
+    data, beg, end = _pack(rows)
+    tabs = {"big": big, "small": small}
+    dev = {name: hip.DeviceScanTables(t) for name, t in tabs.items()}
+    bs2 = hip.ScanBankSet(list(dev.items()))
+    fused2 = hip.scan_multi(data, beg, end, bs2)
+    torch.cuda.synchronize()
+    for name, t in tabs.items():
+        single, _ = hip.scan(data, beg, end, dev[name])
+        torch.cuda.synchronize()
+        assert torch.equal(fused2[bs2.index[name]], single), name
+        got = single.cpu().numpy().astype(np.uint32)
+        for i, row in enumerate(rows):
+            assert int(got[i]) == dfa.match_mask_reference(t, row), (name, i)
+    assert int(fused2[bs2.index["big"]].ne(0).sum()) >= 32 and int(fused2[bs2.index["small"]].ne(0).sum()) >= 8
 
 
 def test_upstream_canonical_gate_number_forms():
