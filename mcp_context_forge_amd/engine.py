@@ -16,6 +16,7 @@ from __future__ import annotations
 import asyncio
 import json
 import logging
+import struct
 import time
 from typing import Any, Dict, List, Optional
 
@@ -397,6 +398,20 @@ class GatewayEngine:
             return list(await asyncio.gather(
                 *(self.handle_rpc_bytes(r, user=u, server_id=server_id) for r, u in zip(raws, users))))
         return list(await asyncio.gather(*(self.handle_rpc_bytes(r, user=user, server_id=server_id) for r in raws)))
+
+    async def process_rpc_packed(self, blob: bytes, offs: bytes, uidx: bytes,
+                                 users: List[Optional[str]]) -> List[Optional[bytes]]:
+        """process_rpc_batch for a batch the native edge already packed:
+        `blob` is every body back to back, `offs` int64 offsets (n + 1),
+        `uidx` an int32 per row into `users` (the batch's distinct users).
+        Row i of the result answers row i of the batch."""
+        if self.gpu_pipeline is not None:
+            return await self.gpu_pipeline.process_packed(blob, offs, uidx, users)
+        n = len(uidx) // 4
+        o = struct.unpack(f"<{n + 1}q", offs)
+        raws = [blob[o[i]:o[i + 1]] for i in range(n)]
+        row_users = [users[k] for k in struct.unpack(f"<{n}i", uidx)]
+        return await self.process_rpc_batch(raws, users=row_users)
 
     def invalidate_peers(self, what: str = "registry") -> None:
         """Publish an invalidation to peer ranks over the RCCL bus (the

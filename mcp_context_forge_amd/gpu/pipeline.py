@@ -95,6 +95,39 @@ class _ToolMeta:
         self.a2a_fast = False       # in-proc agent, hooks fully GPU-covered
 
 
+class _PackedRows:
+    """raws[i] over a joined blob + offsets: a row's bytes exist only once a
+    per-request path (non-tools/call, host-bound, cross-rank forward) asks."""
+
+    __slots__ = ("blob", "offs")
+
+    def __init__(self, blob: bytes, offs: np.ndarray):
+        self.blob = blob
+        self.offs = offs
+
+    def __len__(self) -> int:
+        return max(int(self.offs.shape[0]) - 1, 0)
+
+    def __getitem__(self, i: int) -> bytes:
+        return self.blob[int(self.offs[i]):int(self.offs[i + 1])]
+
+
+class _IndexedUsers:
+    """users[i] over the batch's distinct users + a per-row index."""
+
+    __slots__ = ("users", "uidx")
+
+    def __init__(self, users: List[Optional[str]], uidx: np.ndarray):
+        self.users = users
+        self.uidx = uidx
+
+    def __len__(self) -> int:
+        return int(self.uidx.shape[0])
+
+    def __getitem__(self, i: int) -> Optional[str]:
+        return self.users[int(self.uidx[i])]
+
+
 class GpuPluginPipeline:
     def __init__(self, engine, device: str = "cuda"):
         self.engine = engine
@@ -667,6 +700,32 @@ class GpuPluginPipeline:
     async def process_batch(self, raws: List[bytes], user: Optional[str] = None,
                             server_id: Optional[str] = None,
                             users: Optional[List[Optional[str]]] = None) -> List[Optional[bytes]]:
+        t0 = self._tic()
+        joined, offs_raw = self._pb.concat_with_offsets(raws)
+        return await self._process_joined(joined, offs_raw, raws, user, server_id, users, None, t0)
+
+    async def process_packed(self, blob: bytes, offs: bytes, uidx: bytes,
+                             users: List[Optional[str]],
+                             server_id: Optional[str] = None) -> List[Optional[bytes]]:
+        """process_batch for a batch that arrives already joined (the native
+        edge's hot lane): `blob` holds every body back to back, `offs` the
+        int64 offsets (n + 1, concat_with_offsets layout), `uidx` an int32
+        per row into `users`, the batch's distinct users. A row's bytes are
+        materialised only where a per-request path needs them, and tenant
+        hashes cost one tool_hash per distinct user."""
+        t0 = self._tic()
+        ui = np.frombuffer(uidx, dtype=np.int32)
+        table = np.array([tool_hash(u or "") for u in users], dtype=np.int64)
+        uh_all = table[ui] if ui.size else np.empty(0, dtype=np.int64)
+        rows = _PackedRows(blob, np.frombuffer(offs, dtype=np.int64))
+        return await self._process_joined(blob, offs, rows, None, server_id,
+                                          _IndexedUsers(users, ui), uh_all, t0)
+
+    async def _process_joined(self, joined: bytes, offs_raw: bytes, raws, user: Optional[str],
+                              server_id: Optional[str], users, uh_all: Optional[np.ndarray],
+                              t0: float) -> List[Optional[bytes]]:
+        """Shared body of process_batch / process_packed. `raws` and `users`
+        are only indexed (`raws[i]`, `users[i]`), so lazy views work."""
         self.batches += 1
         n = len(raws)
         self.requests += n
@@ -675,8 +734,6 @@ class GpuPluginPipeline:
         def row_user(i: int) -> Optional[str]:
             return users[i] if users is not None else user
 
-        t0 = self._tic()
-        joined, offs_raw = self._pb.concat_with_offsets(raws)
         offsets = np.frombuffer(offs_raw, dtype=np.int64)
         blob = np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, dtype=np.uint8)
         env = hip.parse_envelopes(blob, offsets)
@@ -694,7 +751,8 @@ class GpuPluginPipeline:
 
         fast_rows = np.nonzero(kind == hip.ENV_TOOLS_CALL)[0]
         if fast_rows.size:
-            await self._fast_toolcalls(raws, blob, env, fast_rows, responses, user, server_id, users)
+            await self._fast_toolcalls(raws, blob, env, fast_rows, responses, user, server_id, users,
+                                       uh_all=uh_all)
         return responses
 
     # ------------------------------------------------------------------
@@ -716,13 +774,15 @@ class GpuPluginPipeline:
     async def _fast_toolcalls(self, raws: List[bytes], blob: np.ndarray, env: dict,
                               rows: np.ndarray, responses: List[Optional[bytes]],
                               user: Optional[str], server_id: Optional[str],
-                              users: Optional[List[Optional[str]]] = None) -> None:
+                              users: Optional[List[Optional[str]]] = None,
+                              uh_all: Optional[np.ndarray] = None) -> None:
         self._meta()  # refresh tool tables on registry/plugin change
         m = rows.shape[0]
         # per-row tenant hash: cache identities (semantic + exact) are
         # (tool, user)-scoped so results never cross users (63-bit so the
-        # XOR with tool_hash stays in int64 domain)
-        if users is not None:
+        # XOR with tool_hash stays in int64 domain). The packed entry passes
+        # them in already gathered (one tool_hash per distinct user).
+        if uh_all is None and users is not None:
             memo: Dict[Optional[str], int] = {}
             uh_all = np.empty(len(users), dtype=np.int64)
             for _i, _u in enumerate(users):
@@ -730,8 +790,6 @@ class GpuPluginPipeline:
                 if _h is None:
                     _h = memo[_u] = tool_hash(_u or "")
                 uh_all[_i] = _h
-        else:
-            uh_all = None
         _uh_scalar = tool_hash(user or "")
         uh = uh_all[rows] if uh_all is not None else np.full(m, _uh_scalar, dtype=np.int64)
         nb = np.ascontiguousarray(env["name_beg"][rows])

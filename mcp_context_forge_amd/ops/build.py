@@ -56,7 +56,8 @@ def build_edge(force: bool = False, verbose: bool = True) -> Path:
     """Native epoll HTTP edge (CPython extension, plain g++ — no HIP):
     forge_edge.so in-tree so the gpurun snapshot ships it."""
     src = CSRC / "edge.cpp"
-    if not force and EDGE.exists() and EDGE.stat().st_mtime > src.stat().st_mtime:
+    newest = max(src.stat().st_mtime, (CSRC / "edge_pack.hpp").stat().st_mtime)
+    if not force and EDGE.exists() and EDGE.stat().st_mtime > newest:
         return EDGE
     import sysconfig
 

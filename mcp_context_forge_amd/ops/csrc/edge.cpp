@@ -18,6 +18,9 @@
 //     load-balances connections), level-triggered epoll, non-blocking fds.
 //   * One global request queue feeds Python: edge_poll() blocks (GIL
 //     released) on a condition variable and drains up to max_n requests.
+//     edge_poll_packed() drains the same way and hands the batch over as
+//     two lanes (edge_pack.hpp): the hot lane as one blob + offsets + a
+//     per-row index into the batch's distinct users, the rest per row.
 //   * Completions (edge_complete) run on the Python caller's thread: format
 //     the HTTP response, append to the connection's output buffer under its
 //     mutex, flush; EAGAIN / close / resume-parse work is bounced to the
@@ -62,7 +65,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "edge_pack.hpp"
+
 namespace {
+
+using edgepack::format_response;
+using edgepack::K_OTHER;
+using edgepack::K_RPC;
+using edgepack::Req;
 
 constexpr size_t MAX_HEADER = 16 * 1024;
 constexpr double NEG_TTL = 2.0;  // seconds a failed-auth memo is trusted
@@ -74,8 +84,6 @@ double mono_s() {
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + ts.tv_nsec * 1e-9;
 }
-
-enum ReqKind : uint8_t { K_RPC = 0, K_OTHER = 1 };
 
 struct Conn {
     std::mutex mu;
@@ -95,15 +103,6 @@ struct Conn {
     bool keep_alive = true;
     uint8_t kind = K_RPC;
     std::string method, target, authz, headers_blob;
-};
-
-struct Req {
-    uint64_t id = 0;
-    uint8_t kind = K_RPC;
-    std::string body;
-    const std::string* user = nullptr;  // interned; null = unresolved
-    std::string authz;                  // raw header value when unresolved
-    std::string method, target, headers_blob;  // K_OTHER only
 };
 
 struct EdgeThread;
@@ -131,7 +130,17 @@ struct Edge {
     std::atomic<uint64_t> accepted{0}, closed_conns{0}, hot{0}, cold{0},
         direct_401{0}, direct_health{0}, responses{0}, bytes_in{0}, bytes_out{0},
         parse_errors{0};
+    // cumulative host-plane cost of the Python boundary: ns spent building
+    // Python objects in poll/poll_packed, ns spent in complete/complete_list,
+    // and how the drained rows split into lanes
+    std::atomic<uint64_t> poll_pack_ns{0}, complete_ns{0}, hot_rows{0}, slow_rows{0};
 };
+
+uint64_t mono_ns() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
 
 struct EdgeThread {
     Edge* e = nullptr;
@@ -176,32 +185,6 @@ struct EdgeThread {
 
 uint64_t make_id(int tid, uint32_t slot, uint32_t gen) {
     return ((uint64_t)(unsigned)tid << 56) | ((uint64_t)(gen & 0xFFFFFF) << 32) | slot;
-}
-
-const char* reason_of(int code) {
-    switch (code) {
-        case 200: return "OK";
-        case 202: return "Accepted";
-        case 400: return "Bad Request";
-        case 401: return "Unauthorized";
-        case 403: return "Forbidden";
-        case 404: return "Not Found";
-        case 413: return "Payload Too Large";
-        case 429: return "Too Many Requests";
-        case 431: return "Request Header Fields Too Large";
-        case 501: return "Not Implemented";
-        default: return "Internal Server Error";
-    }
-}
-
-void format_response(std::string& out, int code, const char* body, size_t n, bool keep_alive) {
-    char head[160];
-    int hn = snprintf(head, sizeof(head),
-                      "HTTP/1.1 %d %s\r\nContent-Type: application/json\r\n"
-                      "Content-Length: %zu\r\nConnection: %s\r\n\r\n",
-                      code, reason_of(code), n, keep_alive ? "keep-alive" : "close");
-    out.append(head, (size_t)hn);
-    out.append(body, n);
 }
 
 // flush c->out on the socket; arm EPOLLOUT on partial. caller holds c->mu.
@@ -648,35 +631,32 @@ PyObject* py_edge_start(PyObject*, PyObject* args) {
     return PyLong_FromVoidPtr(e);
 }
 
-PyObject* py_edge_poll(PyObject*, PyObject* args) {
-    unsigned long long handle;
-    int wait_us, linger_us, max_n;
-    if (!PyArg_ParseTuple(args, "Kiii", &handle, &wait_us, &linger_us, &max_n)) return nullptr;
-    Edge* e = (Edge*)(uintptr_t)handle;
-    std::vector<Req> batch;
-    Py_BEGIN_ALLOW_THREADS;
-    {
-        std::unique_lock<std::mutex> g(e->qmu);
-        if (e->queue.empty() && wait_us > 0) {
-            e->qcv.wait_for(g, std::chrono::microseconds(wait_us),
-                            [&] { return !e->queue.empty() || e->stop.load(); });
-        }
-        if (!e->queue.empty() && linger_us > 0 && (int)e->queue.size() < max_n) {
-            g.unlock();
-            std::this_thread::sleep_for(std::chrono::microseconds(linger_us));
-            g.lock();
-        }
-        int n = (int)e->queue.size();
-        if (n > max_n) n = max_n;
-        batch.reserve((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            batch.push_back(std::move(e->queue.front()));
-            e->queue.pop_front();
-        }
+// wait/linger/drain shared by poll and poll_packed. Call with the GIL released.
+void drain_queue(Edge* e, int wait_us, int linger_us, int max_n, std::vector<Req>& batch) {
+    std::unique_lock<std::mutex> g(e->qmu);
+    if (e->queue.empty() && wait_us > 0) {
+        e->qcv.wait_for(g, std::chrono::microseconds(wait_us),
+                        [&] { return !e->queue.empty() || e->stop.load(); });
     }
-    Py_END_ALLOW_THREADS;
+    if (!e->queue.empty() && linger_us > 0 && (int)e->queue.size() < max_n) {
+        g.unlock();
+        std::this_thread::sleep_for(std::chrono::microseconds(linger_us));
+        g.lock();
+    }
+    int n = (int)e->queue.size();
+    if (n > max_n) n = max_n;
+    if (n < 0) n = 0;
+    batch.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        batch.push_back(std::move(e->queue.front()));
+        e->queue.pop_front();
+    }
+}
 
-    size_t n = batch.size();
+// per-row shape (ids, kinds, bodies, users, authzs, meta) over the rows of
+// `batch` that `idx` names (all rows when idx is null)
+PyObject* build_rows(const std::vector<Req>& batch, const std::vector<uint32_t>* idx) {
+    size_t n = idx ? idx->size() : batch.size();
     PyObject* ids = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(n * 8));
     PyObject* kinds = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)n);
     PyObject* bodies = PyList_New((Py_ssize_t)n);
@@ -687,7 +667,7 @@ PyObject* py_edge_poll(PyObject*, PyObject* args) {
     uint64_t* idp = (uint64_t*)PyBytes_AS_STRING(ids);
     char* kp = PyBytes_AS_STRING(kinds);
     for (size_t i = 0; i < n; ++i) {
-        Req& r = batch[i];
+        const Req& r = batch[idx ? (*idx)[i] : i];
         idp[i] = r.id;
         kp[i] = (char)r.kind;
         PyList_SET_ITEM(bodies, (Py_ssize_t)i,
@@ -719,11 +699,98 @@ PyObject* py_edge_poll(PyObject*, PyObject* args) {
     return Py_BuildValue("(NNNNNN)", ids, kinds, bodies, users, authzs, meta);
 }
 
+PyObject* py_edge_poll(PyObject*, PyObject* args) {
+    unsigned long long handle;
+    int wait_us, linger_us, max_n;
+    if (!PyArg_ParseTuple(args, "Kiii", &handle, &wait_us, &linger_us, &max_n)) return nullptr;
+    Edge* e = (Edge*)(uintptr_t)handle;
+    std::vector<Req> batch;
+    Py_BEGIN_ALLOW_THREADS;
+    drain_queue(e, wait_us, linger_us, max_n, batch);
+    Py_END_ALLOW_THREADS;
+
+    uint64_t t0 = mono_ns();
+    size_t hot = 0;
+    for (const Req& r : batch) hot += edgepack::is_hot(r) ? 1 : 0;
+    e->hot_rows += hot;
+    e->slow_rows += batch.size() - hot;
+    PyObject* out = build_rows(batch, nullptr);
+    e->poll_pack_ns += mono_ns() - t0;
+    return out;
+}
+
+// poll_packed: same queue / linger / max_n logic as poll, but the batch comes
+// back split into lanes (edge_pack.hpp). The hot lane costs O(1) Python
+// objects per batch plus one str per DISTINCT user; the slow lane keeps
+// poll's per-row shape.
+//   -> (ids u64[h], blob, offs i64[h+1], uidx i32[h], users list[str|None],
+//       ucount list[int], slow (ids, kinds, bodies, users, authzs, meta))
+PyObject* py_edge_poll_packed(PyObject*, PyObject* args) {
+    unsigned long long handle;
+    int wait_us, linger_us, max_n;
+    if (!PyArg_ParseTuple(args, "Kiii", &handle, &wait_us, &linger_us, &max_n)) return nullptr;
+    Edge* e = (Edge*)(uintptr_t)handle;
+    std::vector<Req> batch;
+    edgepack::LanePlan plan;
+    Py_BEGIN_ALLOW_THREADS;
+    drain_queue(e, wait_us, linger_us, max_n, batch);
+    edgepack::plan_lanes(batch, plan);
+    Py_END_ALLOW_THREADS;
+
+    uint64_t t0 = mono_ns();
+    size_t h = plan.hot.size();
+    e->hot_rows += h;
+    e->slow_rows += plan.slow.size();
+    PyObject* ids = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(h * 8));
+    PyObject* blob = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)plan.blob_bytes);
+    PyObject* offs = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)((h + 1) * 8));
+    PyObject* uidx = PyBytes_FromStringAndSize((const char*)plan.uidx.data(), (Py_ssize_t)(h * 4));
+    PyObject* users = PyList_New((Py_ssize_t)plan.users.size());
+    PyObject* ucount = PyList_New((Py_ssize_t)plan.users.size());
+    PyObject* slow = build_rows(batch, &plan.slow);
+    if (!ids || !blob || !offs || !uidx || !users || !ucount || !slow) {
+        Py_XDECREF(ids); Py_XDECREF(blob); Py_XDECREF(offs); Py_XDECREF(uidx);
+        Py_XDECREF(users); Py_XDECREF(ucount); Py_XDECREF(slow);
+        return nullptr;
+    }
+    edgepack::pack_hot(batch, plan, (uint64_t*)PyBytes_AS_STRING(ids), PyBytes_AS_STRING(blob),
+                       (int64_t*)PyBytes_AS_STRING(offs));
+    for (size_t k = 0; k < plan.users.size(); ++k) {
+        const std::string* u = plan.users[k];
+        PyObject* us;
+        if (u != nullptr) {
+            us = PyUnicode_FromStringAndSize(u->data(), (Py_ssize_t)u->size());
+        } else {
+            Py_INCREF(Py_None);
+            us = Py_None;
+        }
+        PyList_SET_ITEM(users, (Py_ssize_t)k, us);
+        PyList_SET_ITEM(ucount, (Py_ssize_t)k, PyLong_FromLongLong((long long)plan.ucount[k]));
+    }
+    e->poll_pack_ns += mono_ns() - t0;
+    return Py_BuildValue("(NNNNNNN)", ids, blob, offs, uidx, users, ucount, slow);
+}
+
+struct DoneItem { uint64_t id; int status; const char* body; size_t n; };
+
+// format + queue every response with the GIL released, one deferred wake per
+// epoll thread; returns how many connections were still there
+uint64_t complete_items(Edge* e, const std::vector<DoneItem>& items) {
+    uint64_t done = 0;
+    std::vector<std::vector<uint32_t>> wake(e->threads.size());
+    for (const DoneItem& it : items)
+        if (complete_one(e, it.id, it.status, it.body, it.n, false, &wake)) done++;
+    for (size_t t = 0; t < wake.size(); ++t)
+        e->threads[t]->wake_with_many(std::move(wake[t]));
+    return done;
+}
+
 PyObject* py_edge_complete(PyObject*, PyObject* args) {
     unsigned long long handle;
     PyObject *ids_b, *statuses_b, *bodies;
     if (!PyArg_ParseTuple(args, "KSSO", &handle, &ids_b, &statuses_b, &bodies)) return nullptr;
     Edge* e = (Edge*)(uintptr_t)handle;
+    uint64_t t0 = mono_ns();
     Py_ssize_t n = PyBytes_GET_SIZE(ids_b) / 8;
     if (PyBytes_GET_SIZE(statuses_b) < n * 2 || !PyList_Check(bodies) || PyList_GET_SIZE(bodies) < n) {
         PyErr_SetString(PyExc_ValueError, "edge_complete: length mismatch");
@@ -759,6 +826,58 @@ PyObject* py_edge_complete(PyObject*, PyObject* args) {
             e->threads[t]->wake_with_many(std::move(wake[t]));
     }
     Py_END_ALLOW_THREADS;
+    e->complete_ns += mono_ns() - t0;
+    return PyLong_FromUnsignedLongLong(done);
+}
+
+// complete_list(handle, ids, bodies): the hot lane's completion. Status comes
+// from the body: None -> 202 with an empty body, bytes -> 200. Nothing is
+// copied under the GIL: (pointer, length) pairs are gathered while this call
+// holds a reference to `bodies`, and the responses are formatted straight
+// into each connection's output buffer with the GIL released.
+// CONTRACT: the caller must not mutate `bodies` (nor a bytearray in it) until
+// the call returns — the list is what keeps the borrowed pointers alive.
+PyObject* py_edge_complete_list(PyObject*, PyObject* args) {
+    unsigned long long handle;
+    PyObject *ids_b, *bodies;
+    if (!PyArg_ParseTuple(args, "KSO!", &handle, &ids_b, &PyList_Type, &bodies)) return nullptr;
+    Edge* e = (Edge*)(uintptr_t)handle;
+    uint64_t t0 = mono_ns();
+    Py_ssize_t n = PyBytes_GET_SIZE(ids_b) / 8;
+    if (PyList_GET_SIZE(bodies) != n) {
+        PyErr_SetString(PyExc_ValueError, "edge_complete_list: length mismatch");
+        return nullptr;
+    }
+    const uint64_t* idp = (const uint64_t*)PyBytes_AS_STRING(ids_b);
+    std::vector<DoneItem> items((size_t)n);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        PyObject* b = PyList_GET_ITEM(bodies, i);
+        DoneItem& it = items[(size_t)i];
+        it.id = idp[i];
+        if (b == Py_None) {
+            it.status = 202;
+            it.body = "";
+            it.n = 0;
+        } else if (PyBytes_Check(b)) {
+            it.status = 200;
+            it.body = PyBytes_AS_STRING(b);
+            it.n = (size_t)PyBytes_GET_SIZE(b);
+        } else if (PyByteArray_Check(b)) {
+            it.status = 200;
+            it.body = PyByteArray_AS_STRING(b);
+            it.n = (size_t)PyByteArray_GET_SIZE(b);
+        } else {
+            PyErr_SetString(PyExc_TypeError, "edge_complete_list: bodies must be bytes or None");
+            return nullptr;
+        }
+    }
+    uint64_t done = 0;
+    Py_INCREF(bodies);
+    Py_BEGIN_ALLOW_THREADS;
+    done = complete_items(e, items);
+    Py_END_ALLOW_THREADS;
+    Py_DECREF(bodies);
+    e->complete_ns += mono_ns() - t0;
     return PyLong_FromUnsignedLongLong(done);
 }
 
@@ -813,7 +932,7 @@ PyObject* py_edge_stats(PyObject*, PyObject* args) {
     if (!PyArg_ParseTuple(args, "K", &handle)) return nullptr;
     Edge* e = (Edge*)(uintptr_t)handle;
     return Py_BuildValue(
-        "{s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K}",
+        "{s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K,s:K}",
         "accepted", (unsigned long long)e->accepted.load(),
         "closed", (unsigned long long)e->closed_conns.load(),
         "hot", (unsigned long long)e->hot.load(),
@@ -823,7 +942,11 @@ PyObject* py_edge_stats(PyObject*, PyObject* args) {
         "responses", (unsigned long long)e->responses.load(),
         "bytes_in", (unsigned long long)e->bytes_in.load(),
         "bytes_out", (unsigned long long)e->bytes_out.load(),
-        "parse_errors", (unsigned long long)e->parse_errors.load());
+        "parse_errors", (unsigned long long)e->parse_errors.load(),
+        "poll_pack_us", (unsigned long long)(e->poll_pack_ns.load() / 1000),
+        "complete_us", (unsigned long long)(e->complete_ns.load() / 1000),
+        "hot_rows", (unsigned long long)e->hot_rows.load(),
+        "slow_rows", (unsigned long long)e->slow_rows.load());
 }
 
 PyObject* py_edge_stop(PyObject*, PyObject* args) {
@@ -847,6 +970,12 @@ PyMethodDef edge_methods[] = {
      "poll(handle, wait_us, linger_us, max_n) -> (ids, kinds, bodies, users, authz, meta)"},
     {"complete", py_edge_complete, METH_VARARGS,
      "complete(handle, ids: bytes, statuses: bytes u16, bodies: list[bytes|None]) -> n_done"},
+    {"poll_packed", py_edge_poll_packed, METH_VARARGS,
+     "poll_packed(handle, wait_us, linger_us, max_n) -> (ids, blob, offs, uidx, users, ucount, "
+     "slow=(ids, kinds, bodies, users, authz, meta))"},
+    {"complete_list", py_edge_complete_list, METH_VARARGS,
+     "complete_list(handle, ids: bytes, bodies: list[bytes|None]) -> n_done; None answers 202, "
+     "bytes 200. The caller must not mutate bodies during the call."},
     {"complete_raw", py_edge_complete_raw, METH_VARARGS,
      "complete_raw(handle, id, raw_http_bytes) -> bool"},
     {"auth_put", py_edge_auth_put, METH_VARARGS, "auth_put(handle, authz: bytes, user: str|None)"},

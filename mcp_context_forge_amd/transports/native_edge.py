@@ -7,10 +7,15 @@ Python authority — it authenticates cache misses, runs the engine's batched
 GPU pipeline over each drained batch, and serves control-plane (non-/rpc)
 requests through the regular ASGI app.
 
-One asyncio task pulls batches with edge.poll (GIL released while waiting),
-processes them, and completes them back to C++; while Python is busy with
-batch N the C++ side accumulates batch N+1 — the micro-batch window emerges
-from load instead of a timer, same serial-consumer shape as
+One asyncio task pulls batches with edge.poll_packed (GIL released while
+waiting), processes them, and completes them back to C++. The hot lane of a
+batch (requests the C++ auth memo already resolved) crosses into Python as a
+handful of flat buffers and leaves through edge.complete_list, so this loop
+does no per-request work for it; only the slow lane (auth misses, scoped
+tokens, control-plane requests) is walked row by row. FORGE_EDGE_PACKED=0
+selects the per-row edge.poll / edge.complete path instead. While Python is
+busy with batch N the C++ side accumulates batch N+1 — the micro-batch
+window emerges from load instead of a timer, same serial-consumer shape as
 gpu/collector.py.
 """
 
@@ -19,6 +24,7 @@ from __future__ import annotations
 import asyncio
 import importlib.util
 import logging
+import os
 import struct
 import time
 from typing import Dict, List, Optional, Tuple
@@ -70,6 +76,10 @@ class NativeEdge:
         self.batches = 0
         self.requests = 0
         self.max_batch = 0
+        self.packed = os.environ.get("FORGE_EDGE_PACKED", "1") != "0"
+        # wall seconds spent in the batch handlers outside the awaited engine
+        # calls: what this loop itself costs per batch
+        self.glue_s = 0.0
 
     # ------------------------------------------------------------------
     async def start(self) -> None:
@@ -97,7 +107,8 @@ class NativeEdge:
             self.handle = 0
 
     def stats(self) -> dict:
-        out = {"batches": self.batches, "requests": self.requests, "max_batch": self.max_batch}
+        out = {"batches": self.batches, "requests": self.requests, "max_batch": self.max_batch,
+               "packed": self.packed, "glue_ms": round(self.glue_s * 1000.0, 3)}
         if self.handle:
             out.update(self.edge.stats(self.handle))
         return out
@@ -145,10 +156,12 @@ class NativeEdge:
         linger_us = s.gpu_batch_window_us
         max_n = s.gpu_batch_max_requests
         sem = asyncio.Semaphore(self.depth)
+        poll = self.edge.poll_packed if self.packed else self.edge.poll
+        handle = self._handle_packed if self.packed else self._handle_batch
 
         async def run_one(batch):
             try:
-                await self._handle_batch(*batch)
+                await handle(*batch)
             except Exception:
                 logger.exception("native edge batch error")
             finally:
@@ -157,9 +170,9 @@ class NativeEdge:
         while self._running:
             try:
                 await sem.acquire()
-                ids, kinds, bodies, users, authzs, meta = await asyncio.to_thread(
-                    self.edge.poll, self.handle, wait_us, linger_us, max_n)
-                n = len(bodies)
+                batch = await asyncio.to_thread(poll, self.handle, wait_us, linger_us, max_n)
+                # packed: hot ids are 8 bytes a row, batch[6] is the slow lane
+                n = len(batch[0]) // 8 + len(batch[6][2]) if self.packed else len(batch[2])
                 if n == 0:
                     sem.release()
                     continue
@@ -167,7 +180,7 @@ class NativeEdge:
                 self.batches += 1
                 self.requests += n
                 self.max_batch = max(self.max_batch, n)
-                asyncio.ensure_future(run_one((ids, kinds, bodies, users, authzs, meta)))
+                asyncio.ensure_future(run_one(batch))
             except asyncio.CancelledError:
                 return
             except Exception:
@@ -176,6 +189,17 @@ class NativeEdge:
                 await asyncio.sleep(0.05)
 
     async def _handle_batch(self, ids: bytes, kinds: bytes, bodies, users, authzs, meta) -> None:
+        t_in = time.perf_counter()
+        eng = 0.0   # seconds inside awaited engine calls
+        try:
+            eng = await self._handle_rows(ids, kinds, bodies, users, authzs, meta)
+        finally:
+            self.glue_s += time.perf_counter() - t_in - eng
+
+    async def _handle_rows(self, ids: bytes, kinds: bytes, bodies, users, authzs, meta) -> float:
+        """The per-row path (FORGE_EDGE_PACKED=0). Returns the seconds spent
+        inside awaited engine calls."""
+        eng = 0.0
         n = len(bodies)
         statuses = bytearray(n * 2)
         outs: List[Optional[bytes]] = [None] * n
@@ -209,7 +233,9 @@ class NativeEdge:
             for u in hot_users:
                 self.engine.token_usage.record(f"user:{u}" if u else "anonymous", u)
             raws = [bodies[i] for i in hot_idx]
+            t_e = time.perf_counter()
             results = await self.engine.process_rpc_batch(raws, users=hot_users)
+            eng += time.perf_counter() - t_e
             for i, r in zip(hot_idx, results):
                 if r is None:
                     struct.pack_into("<H", statuses, i * 2, 202)
@@ -219,7 +245,9 @@ class NativeEdge:
                     outs[i] = r if isinstance(r, bytes) else bytes(r)
 
         for i, ctx in scoped:
+            t_e = time.perf_counter()
             r = await self.engine.handle_rpc_bytes(bodies[i], user=ctx.user, server_id=ctx.server_id)
+            eng += time.perf_counter() - t_e
             struct.pack_into("<H", statuses, i * 2, 200 if r is not None else 202)
             outs[i] = r or b""
 
@@ -233,6 +261,101 @@ class NativeEdge:
         for i in cold:
             (rid,) = struct.unpack_from("<Q", ids, i * 8)
             asyncio.ensure_future(self._cold_one(rid, meta[i], bodies[i], authzs[i]))
+        return eng
+
+    # ------------------------------------------------------------------
+    async def _handle_packed(self, ids: bytes, blob: bytes, offs: bytes, uidx: bytes,
+                             users, ucount, slow) -> None:
+        t_in = time.perf_counter()
+        box = [0.0]   # seconds inside awaited engine calls
+        try:
+            await self._handle_lanes(ids, blob, offs, uidx, users, ucount, slow, box)
+        finally:
+            self.glue_s += time.perf_counter() - t_in - box[0]
+
+    async def _handle_lanes(self, ids: bytes, blob: bytes, offs: bytes, uidx: bytes,
+                            users, ucount, slow, box) -> None:
+        """One poll_packed batch. The hot lane (ids/blob/offs/uidx/users/
+        ucount) goes to the engine as it came; the slow lane keeps the
+        per-row logic of _handle_rows."""
+        s_ids, s_kinds, s_bodies, s_users, s_authzs, s_meta = slow
+        denied: List[int] = []
+        scoped: List[Tuple[int, object]] = []       # (idx, ctx) server-scoped tokens
+        promoted: List[Tuple[int, Optional[str]]] = []  # authenticated here, unscoped
+        cold: List[int] = []
+        for i in range(len(s_bodies)):
+            if s_kinds[i] == 0:
+                u = s_users[i]
+                if u is None and s_authzs[i] is not None:
+                    ctx = self._authenticate(s_authzs[i])
+                    if ctx is None:
+                        denied.append(i)
+                        continue
+                    if ctx.server_id is not None:
+                        scoped.append((i, ctx))
+                        continue
+                    u = ctx.user
+                promoted.append((i, u))
+            else:
+                cold.append(i)
+
+        if promoted:
+            # rare (first request of a credential): append to the hot batch
+            h = len(ids) // 8
+            users, ucount = list(users), list(ucount)
+            (last,) = struct.unpack_from("<q", offs, h * 8)
+            add_ids, add_bodies, add_offs, add_uidx = [], [], [], []
+            for i, u in promoted:
+                if u in users:
+                    k = users.index(u)
+                else:
+                    k = len(users)
+                    users.append(u)
+                    ucount.append(0)
+                ucount[k] += 1
+                last += len(s_bodies[i])
+                add_ids.append(s_ids[i * 8:(i + 1) * 8])
+                add_bodies.append(s_bodies[i])
+                add_offs.append(last)
+                add_uidx.append(k)
+            ids += b"".join(add_ids)
+            blob += b"".join(add_bodies)
+            offs += struct.pack(f"<{len(add_offs)}q", *add_offs)
+            uidx += struct.pack(f"<{len(add_uidx)}i", *add_uidx)
+
+        if ids:
+            # usage accounting for the C++-authenticated hot lane (credential
+            # granularity is the user — the native cache intentionally does
+            # not carry token ids): one increment of n per distinct user
+            for u, c in zip(users, ucount):
+                self.engine.token_usage.record(f"user:{u}" if u else "anonymous", u, n=c)
+            t_e = time.perf_counter()
+            results = await self.engine.process_rpc_packed(blob, offs, uidx, users)
+            box[0] += time.perf_counter() - t_e
+            # complete the hot lane first — scoped and cold requests may take
+            # arbitrary time. complete_list reads `results` without the GIL:
+            # nothing may touch the list until the call returns
+            await asyncio.to_thread(self.edge.complete_list, self.handle, ids, results)
+
+        if denied or scoped:
+            d_ids, d_sts, d_bodies = [], [], []
+            for i in denied:
+                d_ids.append(s_ids[i * 8:(i + 1) * 8])
+                d_sts.append(401)
+                d_bodies.append(b'{"detail":"Not authenticated"}')
+            for i, ctx in scoped:
+                t_e = time.perf_counter()
+                r = await self.engine.handle_rpc_bytes(s_bodies[i], user=ctx.user, server_id=ctx.server_id)
+                box[0] += time.perf_counter() - t_e
+                d_ids.append(s_ids[i * 8:(i + 1) * 8])
+                d_sts.append(200 if r is not None else 202)
+                d_bodies.append(r or b"")
+            await asyncio.to_thread(self.edge.complete, self.handle, b"".join(d_ids),
+                                    struct.pack(f"<{len(d_sts)}H", *d_sts), d_bodies)
+
+        for i in cold:
+            (rid,) = struct.unpack_from("<Q", s_ids, i * 8)
+            asyncio.ensure_future(self._cold_one(rid, s_meta[i], s_bodies[i], s_authzs[i]))
 
     # ------------------------------------------------------------------
     async def _cold_one(self, rid: int, m, body: bytes, authz: Optional[bytes]) -> None:
