@@ -39,7 +39,17 @@ chain):
     raw bytes for rows with NO escape triggers — wire forms that differ
     from canonical text only by whitespace/key order can score differently
     near the threshold. Rows with triggers are re-scored over canonical
-    text on the host path.
+    text on the host path;
+  * secrets_detection is an exact prefilter over raw bytes: a span with no
+    backslash and no non-ASCII byte holds every decoded string value
+    verbatim between quotes, and '"' is in no entropy alphabet, so every
+    run and every pattern match the CPU plugin can see is present
+    byte-for-byte in the raw span. The bank's DFA patterns are supersets
+    of the plugin's regexes and the entropy compare subtracts TOL (f32 vs
+    f64 rounding), so the prefilter may over-flag (keys, long integers)
+    but never under-flags. Flagged rows, and every span with a backslash
+    or a non-ASCII byte, run the exact CPU plugin
+    (tests/test_secrets_plugin.py checks the containment on the CPU).
 """
 
 from __future__ import annotations
@@ -53,6 +63,7 @@ import numpy as np
 import torch
 
 from ..ops import dfa, hip
+from ..ops.entropy import TOL as ENTROPY_TOL
 from ..protocol import jsonrpc
 from ..plugins.builtin import _walk_strings
 from ..plugins.framework import PluginMode
@@ -151,6 +162,7 @@ class GpuPluginPipeline:
         self.out_guard = plug("output_length_guard")
         self.exact_cache = plug("cached_tool_result")
         self.breaker = plug("circuit_breaker")
+        self.secrets = plug("secrets_detection")
 
         # plugins the fast path MODELS (as GPU banks, post-chain stages or
         # decision flags). Any OTHER tool-hooked plugin in the chain
@@ -160,7 +172,7 @@ class GpuPluginPipeline:
         self._modeled = {"deny_filter", "harmful_content_detector", "pii_filter", "regex_filter",
                          "argument_normalizer", "content_moderation", "response_cache_by_prompt",
                          "schema_guard", "toon_encoder", "output_length_guard",
-                         "cached_tool_result", "circuit_breaker"}
+                         "cached_tool_result", "circuit_breaker", "secrets_detection"}
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -179,6 +191,21 @@ class GpuPluginPipeline:
                 dfa.compile_patterns(
                     ["".join(ch if ch.isalnum() else "\\" + ch for ch in t) if not t.startswith("[") else t
                      for t in _NORMALIZE_TRIGGERS], case_insensitive=False), device)
+
+        # secrets_detection: its format bank plus one symbol table and
+        # threshold per configured entropy alphabet (entropy.hip)
+        self._secret_tabs: List[Tuple[torch.Tensor, float]] = []
+        if self.secrets is not None:
+            tables = self.secrets.scan_tables()
+            if tables is not None:
+                self.banks["secrets"] = hip.DeviceScanTables(tables, device)
+            self._secret_tabs = [(hip.entropy_table(tab, device), thr)
+                                 for (_a, _c, tab, thr) in self.secrets.entropy_detectors]
+            if not self._secret_tabs:
+                # formats only: an empty alphabet still reports the
+                # backslash / non-ASCII bit, which the prefilter needs
+                self._secret_tabs = [(hip.entropy_table(np.full(256, 0xFF, dtype=np.uint8), device),
+                                      float("inf"))]
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -268,7 +295,8 @@ class GpuPluginPipeline:
         # fused multi-bank scans: pass 3's bank set is static; pass 1's
         # includes the per-registry schema bank (rebuilt in _rebuild_tool_meta)
         self._bankset3 = hip.ScanBankSet(
-            [(n, self.banks[n]) for n in ("pii", "regex", "harm", "postmeta") if n in self.banks],
+            [(n, self.banks[n]) for n in ("pii", "regex", "harm", "postmeta", "secrets")
+             if n in self.banks],
             device)
         self._bankset1: Optional[hip.ScanBankSet] = None
         self._graphs = None   # pass-1 GraphCache; rebuilt when _bankset1 changes
@@ -313,6 +341,7 @@ class GpuPluginPipeline:
         self.post_c_punt = 0  # rows the C post lane punted back to Python
         self.py_fallback = 0
         self.host_bound = 0   # requests routed to the CPU chain by plugin bindings
+        self.secrets_routed = 0  # requests the secrets prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         import os as _os
 
@@ -506,7 +535,8 @@ class GpuPluginPipeline:
         # force the full CPU chain for that tool (correctness over speed)
         mgr = self.engine.plugins
         bank_names = {p.name for p in (self.deny, self.pii, self.regex, self.normalizer,
-                                       self.moderation, self.harm, self.schema_guard) if p is not None}
+                                       self.moderation, self.harm, self.schema_guard,
+                                       self.secrets) if p is not None}
         from ..plugins.framework import HookType as _HT
 
         extra_chain = [p for p in mgr.plugins
@@ -523,6 +553,7 @@ class GpuPluginPipeline:
         rw_pii = np.zeros(max(nt, 1), dtype=bool)
         rw_harm = np.zeros(max(nt, 1), dtype=bool)
         mod_app = np.zeros(max(nt, 1), dtype=bool)
+        sec_act = np.zeros(max(nt, 1), dtype=bool)
         for i, m in enumerate(metas):
             bmap = mgr.bindings_for_tool(m.name)
             m.host_chain = any(b.get("config") or (pname not in bank_names)
@@ -590,6 +621,9 @@ class GpuPluginPipeline:
                     pf = -1
                 else:
                     pf |= 4
+            sec_act[i] = self._active(self.secrets, m.name, block_class=False)
+            if sec_act[i]:
+                pf = -1  # flagged results need scan_payload: Python _host_post
             postlane[i] = pf
             rw_norm[i] = self._active(self.normalizer, m.name, block_class=False)
             rw_regex[i] = self._active(self.regex, m.name, block_class=False)
@@ -602,6 +636,7 @@ class GpuPluginPipeline:
         self._t_postlane = postlane
         self._t_rw_norm, self._t_rw_regex, self._t_rw_deny = rw_norm, rw_regex, rw_deny
         self._t_rw_pii, self._t_rw_harm, self._t_mod_app = rw_pii, rw_harm, mod_app
+        self._t_secrets = sec_act if sec_act.any() else None
         # FAST-mode schema descriptors for the C rewrite lane (presence +
         # type checks only — richer schemas never compile to "fast"); a C
         # pass means the exact validator is skipped, a C fail reruns it
@@ -851,13 +886,27 @@ class GpuPluginPipeline:
         # chain (the binding-aware invoke_hook path); everything else stays
         # on the GPU fast path
         hostbound = getattr(self, "_t_hostbound", None)
-        if hostbound is not None:
+        sec_tools = getattr(self, "_t_secrets", None)
+        if hostbound is not None or sec_tools is not None:
             hb_mask = np.zeros(m, dtype=bool)
             valid = tool_idx >= 0
-            hb_mask[valid] = hostbound[tool_idx[valid]]
+            if hostbound is not None:
+                hb_mask[valid] = hostbound[tool_idx[valid]]
+            n_bound = int(hb_mask.sum())
+            if sec_tools is not None:
+                # secrets_detection pre-pass: rows of secrets-active tools
+                # whose raw argument bytes MAY hold a secret leave with the
+                # host-bound rows and run the exact CPU chain, plugin included
+                sec_rows = np.zeros(m, dtype=bool)
+                sec_rows[valid] = sec_tools[tool_idx[valid]]
+                sec_rows &= ~hb_mask
+                if sec_rows.any():
+                    flagged = await self._secrets_prepass(blob, args_b, args_e, sec_rows)
+                    self.secrets_routed += int(flagged.sum())
+                    hb_mask |= flagged
             if hb_mask.any():
                 hb_rows = rows[hb_mask]
-                self.host_bound += int(hb_rows.size)
+                self.host_bound += n_bound
                 outs = await asyncio.gather(
                     *(self.engine.handle_rpc_bytes(
                         raws[int(i)],
@@ -1153,6 +1202,51 @@ class GpuPluginPipeline:
         tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32,
                np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32}[np.dtype(arr.dtype)]
         return dev.view(tdt).reshape(arr.shape)
+
+    def _entropy_flags(self, ent, n: int) -> np.ndarray:
+        """Secrets prefilter over hip.token_entropy outputs, one entry per
+        alphabet as ((max_h, span, n_runs, flags), threshold): a row is
+        flagged when max_h >= threshold - TOL, or when its span holds a
+        backslash or a non-ASCII byte (raw bytes may differ from the
+        decoded strings, so only the host check is exact)."""
+        out = np.zeros(n, dtype=bool)
+        for (max_h, _span, _runs, flags), thr in ent:
+            out |= max_h.cpu().numpy() >= np.float32(thr - ENTROPY_TOL)
+            out |= (flags.cpu().numpy() & 1) != 0
+        return out
+
+    async def _secrets_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
+                               sec_rows: np.ndarray) -> np.ndarray:
+        """secrets_detection prefilter over raw argument bytes → bool[m],
+        True where the row must run the exact CPU chain. Eager, under
+        _gpu_lock: the format bank (scan.hip) and one token_entropy launch
+        per configured alphabet over the secrets-active rows; every other
+        row gets an empty span. The blob is uploaded here and again by pass
+        1 on purpose — folding this pre-pass into the captured pass-1 graph
+        is a later change."""
+        t0 = self._tic()
+        m = args_b.shape[0]
+        sb = np.ascontiguousarray(np.where(sec_rows, args_b, 0).astype(np.int32))
+        se = np.ascontiguousarray(np.where(sec_rows, args_e, 0).astype(np.int32))
+        await self._gpu_lock.acquire()
+        try:
+            self._pin_reset()
+            data_t = self._upload(blob)
+            beg_t = self._upload(sb)
+            end_t = self._upload(se)
+            mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0] \
+                if "secrets" in self.banks else None
+            ent = [(hip.token_entropy(data_t, beg_t, end_t, tab, self.secrets.min_len), thr)
+                   for tab, thr in self._secret_tabs]
+            await self._await_gpu()
+        finally:
+            self._gpu_lock.release()
+        flagged = self._entropy_flags(ent, m)
+        if mask_t is not None:
+            flagged |= mask_t.cpu().numpy() != 0
+        flagged &= sec_rows
+        self._toc("gp0_secrets", t0)
+        return flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1600,13 +1694,16 @@ class GpuPluginPipeline:
         post_flag = np.zeros(n_all, dtype=bool)
         toon_meta = np.zeros(n_all, dtype=bool)
         regex3 = np.zeros(n_all, dtype=bool)
+        sec3 = None  # secrets prefilter verdict per result (secrets-active tools only)
         if n_all:
             await self._gpu_lock.acquire()
             g3 = None
-            if self._graphs3 is None:
-                from .graphs import Pass3Graphs
-                self._graphs3 = Pass3Graphs(self)
-            g3 = self._graphs3.get(n_all, int(res_blob.nbytes))
+            if self.secrets is None:
+                if self._graphs3 is None:
+                    from .graphs import Pass3Graphs
+                    self._graphs3 = Pass3Graphs(self)
+                g3 = self._graphs3.get(n_all, int(res_blob.nbytes))
+            # else: eager, so token_entropy runs on the same uploaded tensors
             if g3 is not None:
                 g3.stage(res_blob, res_beg.astype(np.int32), res_end.astype(np.int32), n_all)
                 g3.replay()
@@ -1622,11 +1719,18 @@ class GpuPluginPipeline:
                 b3 = self._upload(res_beg.astype(np.int32))
                 e3 = self._upload(res_end.astype(np.int32))
                 out3 = hip.scan_multi(data3, b3, e3, self._bankset3)  # fused, one launch
+                ent3 = [(hip.token_entropy(data3, b3, e3, tab, self.secrets.min_len), thr)
+                        for tab, thr in self._secret_tabs] if self.secrets is not None else []
                 try:
                     await self._await_gpu()
                 finally:
                     self._gpu_lock.release()
                 mm3 = out3.cpu().numpy().view(np.uint32)
+                if self.secrets is not None and self._t_secrets is not None:
+                    sec3 = self._entropy_flags(ent3, n_all)
+                    if "secrets" in self._bankset3.index:
+                        sec3 |= mm3[self._bankset3.index["secrets"]] != 0
+                    sec3 &= self._t_secrets[np.clip(tool_idx[all_js_np], 0, None)]
             for b, i in self._bankset3.index.items():
                 h = mm3[i] != 0
                 if b == "postmeta":
@@ -1642,6 +1746,8 @@ class GpuPluginPipeline:
         outschema = self._t_outschema[np.clip(tool_idx[all_js_np], 0, None)] if n_all else np.zeros(0, bool)
         needs_host = post_flag | outschema | (toon_meta & (res_len >= toon_min)) | \
             (res_len > guard_max) | err_rows.astype(bool)
+        if sec3 is not None:
+            needs_host = needs_host | sec3
 
         self._toc("post_scan", t_p)
         t_f = self._tic()
@@ -1817,7 +1923,7 @@ class GpuPluginPipeline:
             st["results"] = []
 
     def _host_post(self, mt: _ToolMeta, rb: bytes) -> Tuple[bytes, bool, Optional[str]]:
-        """Exact host post chain for flagged results: regex(20) → pii(30) →
+        """Exact host post chain for flagged results: secrets(5) → regex(20) → pii(30) →
         output-schema → harm(60) → toon(900) → guard(950)."""
         self.post_rewrites += 1
         try:
@@ -1825,6 +1931,20 @@ class GpuPluginPipeline:
         except Exception:
             return rb, True, None
         name = mt.name
+        if self._active(self.secrets, name, block_class=False):
+            # secrets_detection(5) first, as the plugin's hook plus the
+            # manager's mode handling would: an enforce-mode block ends the
+            # chain, a permissive one is only logged, redact always rewrites.
+            # (Like the rewriters below it sees the upstream result; the
+            # CPU chain checks an output schema before its post hooks, so a
+            # result that violates one is scanned here and not there.)
+            new, findings = self.secrets.scan_payload(result)
+            reason = self.secrets.block_reason(findings)
+            if reason is not None and self.engine.plugins.effective_mode(self.secrets, name) in (
+                    PluginMode.ENFORCE, PluginMode.ENFORCE_IGNORE_ERROR):
+                return rb, True, f"secrets_detection: {reason}"
+            if findings and self.secrets.action == "redact":
+                result = new
         if self._active(self.regex, name, block_class=False):
             result = _walk_strings(result, self.regex.apply_rules)
         if self._active(self.pii, name, block_class=False):
@@ -1884,7 +2004,7 @@ class GpuPluginPipeline:
             "timing_s": {k: round(v, 4) for k, v in self.timing.items()} if self.timing_enabled else None,
             "batches": self.batches, "requests": self.requests, "fast_path": self.fast_path,
             "slow_path": self.slow_path, "blocked": self.blocked, "cache_hits": self.cache_hits,
-            "host_bound": self.host_bound,
+            "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "banks": {k: {"states": v.n_states, "classes": v.n_classes} for k, v in self.banks.items()},

@@ -44,6 +44,14 @@ int forge_scan_multi(const void* data, const void* beg, const void* end_, int ba
                      const void* descs_dev, int n_banks, int lds_bytes,
                      void* out_mask, void* stream);
 
+/* One wave per request: entropy of the in-alphabet runs of at least min_len
+ * bytes. sym is a 256-byte table, symbol 0..63 or 0xFF for a non-member.
+ * out_h f32[batch], out_span i32[batch][2], out_runs / out_flags i32[batch]. */
+int forge_token_entropy(const void* data, const void* beg, const void* end_, int batch,
+                        const void* sym, int min_len,
+                        void* out_h, void* out_span, void* out_runs, void* out_flags,
+                        void* stream);
+
 int forge_featurize(const void* data, const void* beg, const void* end_, int batch, int dim,
                     void* out_bf16, void* out_f32, void* stream);
 

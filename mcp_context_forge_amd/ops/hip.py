@@ -16,6 +16,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import entropy
 from .dfa import ScanTables
 
 
@@ -37,6 +38,7 @@ def _sig(ret: str, args: str):
 _API = {
     "forge_scan": _sig("i", "ppp i ppp ii pp p"),
     "forge_scan_multi": _sig("i", "ppp i p ii p p"),
+    "forge_token_entropy": _sig("i", "ppp i pi pppp p"),
     "forge_featurize": _sig("i", "ppp ii pp p"),
     "forge_json_guard": _sig("i", "ppp i ii pp p"),
     "forge_gemm_bt": _sig("i", "pppp iii ii p"),
@@ -192,6 +194,45 @@ def scan_multi(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor,
         _ptr(bankset.descs), bankset.n, bankset.lds_bytes,
         _ptr(out), _stream()))
     return out
+
+
+# Symbol-table builders for token_entropy (uint8[256] numpy, see ops/entropy.py).
+ENTROPY_BASE64 = entropy.base64_table
+ENTROPY_HEX = entropy.hex_table
+
+
+def entropy_table(sym_table, device: str = "cuda") -> torch.Tensor:
+    """A 256-entry symbol table on the device (upload once, pass to every call)."""
+    t = np.ascontiguousarray(np.asarray(sym_table, dtype=np.uint8).reshape(-1))
+    if t.shape[0] != 256:
+        raise ValueError("symbol table must have 256 entries")
+    return torch.from_numpy(t.copy()).to(device)
+
+
+def token_entropy(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, sym_table,
+                  min_len: int, out: Optional[Tuple[torch.Tensor, ...]] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Entropy of the in-alphabet runs of >= min_len bytes, one wave per
+    request (entropy.hip; oracle ops/entropy.py token_entropy_reference).
+    sym_table: uint8[256] device tensor (entropy_table) or a host array.
+    → (max_h f32[B], span i32[B, 2], n_runs i32[B], flags i32[B]).
+    `out` (those four, preallocated) makes the call graph-capture safe."""
+    batch = beg.numel()
+    if not isinstance(sym_table, torch.Tensor):
+        sym_table = entropy_table(sym_table, str(data.device))
+    if sym_table.dtype != torch.uint8 or sym_table.numel() != 256:
+        raise ValueError("symbol table must be uint8[256]")
+    if out is None:
+        dev = data.device
+        out = (torch.empty(batch, dtype=torch.float32, device=dev),
+               torch.empty((batch, 2), dtype=torch.int32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev))
+    max_h, span, n_runs, flags = out
+    _check("forge_token_entropy", _load().forge_token_entropy(
+        _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(sym_table), int(min_len),
+        _ptr(max_h), _ptr(span), _ptr(n_runs), _ptr(flags), _stream()))
+    return max_h, span, n_runs, flags
 
 
 def featurize(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, dim: int,

@@ -4,6 +4,9 @@ Per-plugin reference analogs (behavioral port, no code copied):
   deny_filter        → plugins/deny_filter/deny.py (deny-list word filter)
   regex_filter       → plugins/regex_filter/search_replace.py
   pii_filter         → cpex-pii-filter (detect/mask emails, SSNs, cards, phones, IPs)
+  secrets_detection  → plugins/secrets_detection (provider key formats + high-entropy
+                       base64/hex tokens; block / redact / audit). Opt-in: not
+                       in the default chain
   schema_guard       → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
@@ -211,6 +214,146 @@ class PIIFilterPlugin(Plugin):
     prompt_pre_fetch = _apply
     agent_pre_invoke = _apply
     agent_post_invoke = _apply
+
+
+# Known secret formats (shared between the CPU re-path and the GPU DFA bank).
+# The DFA pattern is a SUPERSET of the Python regex: the provider prefix plus
+# the first four bytes of the token body, no word boundaries, so wherever the
+# regex matches, the search automaton has matched too. Full-length bodies
+# would be exact but their counters multiply across patterns in the subset
+# construction (the six full patterns exceed 60 000 states; this bank has
+# under 1 000). A prefilter hit only routes the row to the exact host check.
+SECRET_PATTERNS: List[Tuple[str, str, str]] = [
+    # (name, dfa_pattern, python_regex)
+    ("aws_access_key_id", r"A[KS]IA[0-9A-Z]{4}", r"\bA[KS]IA[0-9A-Z]{16}\b"),
+    ("github_token", r"gh[pousr]_[A-Za-z0-9]{4}", r"\bgh[pousr]_[A-Za-z0-9]{36,}"),
+    ("github_fine_grained_pat", r"github_pat_[A-Za-z0-9_]{4}", r"\bgithub_pat_[A-Za-z0-9_]{22,}"),
+    ("slack_token", r"xox[abeoprs]-[A-Za-z0-9\-]{4}", r"\bxox[abeoprs]-[A-Za-z0-9\-]{10,}"),
+    ("google_api_key", r"AIza[0-9A-Za-z_\-]{4}", r"\bAIza[0-9A-Za-z_\-]{35}"),
+    ("pem_private_key", r"-----BEGIN [A-Z ]*PRIVATE KEY-----", r"-----BEGIN (?:[A-Z]+ )*PRIVATE KEY-----"),
+    ("jwt", r"eyJ[A-Za-z0-9_\-]{4,}\.eyJ",
+     r"\beyJ[A-Za-z0-9_\-]{8,}\.eyJ[A-Za-z0-9_\-]{8,}\.[A-Za-z0-9_\-]{8,}"),
+]
+
+# Well-known entropy thresholds (bits per symbol) per alphabet.
+ENTROPY_THRESHOLDS = {"base64": 4.5, "hex": 3.0}
+
+
+class SecretsDetectionPlugin(Plugin):
+    """Stop credentials travelling in arguments or coming back in results:
+    known provider formats (a DFA bank on the GPU path) plus long base64/hex
+    tokens of high Shannon entropy (ops/entropy.py; entropy.hip on the GPU
+    path). Priority 5: it sees the payload before any rewriter in both
+    directions, which is what makes the pipeline's raw-byte prefilter sound.
+
+    Config: action block (default, code "secrets") | redact | audit,
+    redaction_text, min_findings_to_block, categories (subset of the format
+    names and "high_entropy_<alphabet>"), alphabets (["base64"], "hex"
+    optional), min_len (20), thresholds ({"base64": 4.5, "hex": 3.0}).
+    """
+
+    name = "secrets_detection"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.TOOL_POST_INVOKE, HookType.PROMPT_PRE_FETCH,
+             HookType.RESOURCE_POST_FETCH)
+    priority = 5
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import entropy as _entropy
+
+        self._entropy = _entropy
+        self.action: str = self.config.get("action", "block")  # block | redact | audit
+        self.redaction_text: str = str(self.config.get("redaction_text", "[SECRET_REDACTED]"))
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self.min_len = max(int(self.config.get("min_len", 20)), 1)
+        alphabets = list(self.config.get("alphabets") or ["base64"])
+        for a in alphabets:
+            if a not in _entropy.TABLES:
+                raise ValueError(f"unknown entropy alphabet {a!r}")
+        thresholds = {**ENTROPY_THRESHOLDS, **(self.config.get("thresholds") or {})}
+        all_names = [n for n, _, _ in SECRET_PATTERNS] + [f"high_entropy_{a}" for a in alphabets]
+        names = set(self.config.get("categories") or all_names)
+        # bytes regexes: spans are byte offsets, shared with the entropy runs
+        self.active = [(n, d, re.compile(p.encode())) for (n, d, p) in SECRET_PATTERNS if n in names]
+        # (alphabet, category, symbol table, threshold) per enabled entropy detector
+        self.entropy_detectors = [(a, f"high_entropy_{a}", _entropy.TABLES[a](), float(thresholds[a]))
+                                  for a in alphabets if f"high_entropy_{a}" in names]
+        self._tables = dfa.compile_patterns([d for (_, d, _) in self.active]) if self.active else None
+
+    def scan_tables(self) -> Optional[dfa.ScanTables]:
+        return self._tables
+
+    def find_spans(self, raw: bytes) -> List[Tuple[int, int, str]]:
+        """Every finding in one string's UTF-8 bytes as (beg, end, category)."""
+        out: List[Tuple[int, int, str]] = []
+        for name, _d, rx in self.active:
+            for mt in rx.finditer(raw):
+                out.append((mt.start(), mt.end(), name))
+        for _a, cat, table, thr in self.entropy_detectors:
+            runs = self._entropy.token_entropy_reference(raw, table, self.min_len)[0]
+            out.extend((b, b + n, cat) for (b, n, h) in runs if h >= thr)
+        return out
+
+    def _redact(self, raw: bytes, spans: List[Tuple[int, int, str]]) -> bytes:
+        merged: List[List[int]] = []
+        for b, e, _c in sorted(spans):
+            if merged and b <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], e)
+            else:
+                merged.append([b, e])
+        rep = self.redaction_text.encode()
+        parts, pos = [], 0
+        for b, e in merged:
+            parts.append(raw[pos:b])
+            parts.append(rep)
+            pos = e
+        parts.append(raw[pos:])
+        return b"".join(parts)
+
+    def scan_payload(self, payload: Any) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value, shared by the hooks and
+        the GPU pipeline's host lane. → (payload, findings): the payload has
+        every finding's span replaced by redaction_text when action is
+        "redact" (otherwise it is returned as is); findings holds one
+        category name per finding."""
+        findings: List[str] = []
+        redact = self.action == "redact"
+
+        def fn(s: str) -> str:
+            raw = s.encode("utf-8", "surrogatepass")
+            spans = self.find_spans(raw)
+            if not spans:
+                return s
+            findings.extend(c for _b, _e, c in spans)
+            if not redact:
+                return s
+            return self._redact(raw, spans).decode("utf-8", "surrogatepass")
+
+        new_payload = _walk_strings(payload, fn)
+        return (new_payload if redact and findings else payload), findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"secrets detected: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        new_payload, findings = self.scan_payload(ctx.args)
+        if not findings:
+            return PluginResult.ok()
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="secrets")
+        if self.action == "redact":
+            return PluginResult.ok(new_payload, secrets=sorted(set(findings)))
+        return PluginResult.ok(secrets=sorted(set(findings)))  # audit: annotate only
+
+    tool_pre_invoke = _apply
+    tool_post_invoke = _apply
+    prompt_pre_fetch = _apply
+    resource_post_fetch = _apply
 
 
 class SchemaGuardPlugin(Plugin):
@@ -604,6 +747,7 @@ BUILTIN_PLUGINS = {
         DenyFilterPlugin,
         RegexFilterPlugin,
         PIIFilterPlugin,
+        SecretsDetectionPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
