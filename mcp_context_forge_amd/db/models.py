@@ -7,7 +7,7 @@ Role :1154, tokens :5338-5697, StructuredLogEntry :6141, audit :6624) on
 SQLAlchemy 2.0, trimmed to the columns the runtime actually consults.
 Durability lives here (SQLite/Postgres); the *hot* lookup structures are
 the in-memory registry caches plus the GPU pipeline's native toolmap and
-per-tool flag tables (gpu/pipeline.py:_rebuild_tool_meta); HBM holds the
+per-tool flag tables (gpu/tooltable.py:build_tool_table); HBM holds the
 scan banks, classifier weights and semantic-cache key matrix.
 """
 

@@ -15,8 +15,8 @@ Correctness containment: the graph executes the exact same kernels with
 the same tensors as the eager path; the GPU parity fuzz exercises the
 pipeline with graphs on. FORGE_PASS1_GRAPH=0 disables capture (eager
 fallback) for A/B checks. Graphs bake the bank-table device pointers,
-so the cache is dropped whenever the tool registry rebuilds
-_bankset1 (pipeline._rebuild_tool_meta)."""
+so every ToolTable gets a new pass-1 cache for its own bank set
+(gpu/tooltable.py:build_tool_table, attached in pipeline._meta)."""
 
 from __future__ import annotations
 
@@ -152,8 +152,8 @@ class GraphCache:
         return None
 
 
-def Pass1Graphs(pipeline):
-    return GraphCache(pipeline, pipeline._bankset1,
+def Pass1Graphs(pipeline, bankset1):
+    return GraphCache(pipeline, bankset1,
                       with_classifier=pipeline.classifier is not None)
 
 

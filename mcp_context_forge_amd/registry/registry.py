@@ -5,7 +5,7 @@ CRUD + mcpgateway/cache/{tool_lookup_cache,registry_cache}. The reference
 caches lookups in Redis; here the hot name→tool mapping is an in-process
 dict plus, when the GPU pipeline is attached, a native C++ toolmap and
 flat per-tool flag tables rebuilt on every registry generation bump
-(gpu/pipeline.py:_rebuild_tool_meta) — name resolution for a whole
+(gpu/tooltable.py:build_tool_table) — name resolution for a whole
 micro-batch is one C call, never a DB or network hop. The DB is
 durability only. (What lives in HBM proper: the DFA scan banks, the
 classifier weights and the semantic-cache key matrix — the decision

@@ -215,7 +215,7 @@ def test_a2a_fast_lane_parity():
             else:
                 assert co["result"] == go["result"], (i, co, go)
         # the fast lane actually engaged
-        mt = gpu.gpu_pipeline._tool_meta["fastbot-chat"]
+        mt = gpu.gpu_pipeline._tools.by_name["fastbot-chat"]
         assert mt.a2a_fast
         await cpu.shutdown()
         await gpu.shutdown()
@@ -258,9 +258,9 @@ def test_pass1_graph_matches_eager():
                              f'{{"name":"t-echo","arguments":{{"m":"row {i} a@b.co","n":{i}}}}}}}').encode())
         out_graph = await e.process_rpc_batch(list(raws))
         pipe = e.gpu_pipeline
-        assert pipe._graphs is not None and pipe._graphs.replays >= 1, \
+        assert pipe._tools.graphs is not None and pipe._tools.graphs.replays >= 1, \
             "graph path did not engage"
-        pipe._graphs.disabled = True
+        pipe._tools.graphs.disabled = True
         out_eager = await e.process_rpc_batch(list(raws))
         assert out_graph == out_eager
         await e.shutdown()

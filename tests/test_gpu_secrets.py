@@ -341,7 +341,7 @@ def test_pipeline_noop_without_the_plugin(monkeypatch):
         assert all(b'"result"' in o for o in out)
         st = pipe.stats()
         assert st["secrets_routed"] == 0 and "gp0_secrets" not in st["timing_s"]
-        assert "secrets" not in pipe._bankset3.index and pipe._t_secrets is None
+        assert "secrets" not in pipe._bankset3.index and pipe._tools.secrets is None
         await gpu.shutdown()
 
     asyncio.run(run())
