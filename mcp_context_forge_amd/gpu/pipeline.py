@@ -49,7 +49,18 @@ chain):
     f64 rounding), so the prefilter may over-flag (keys, long integers)
     but never under-flags. Flagged rows, and every span with a backslash
     or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_secrets_plugin.py checks the containment on the CPU).
+    (tests/test_secrets_plugin.py checks the containment on the CPU);
+  * encoded_exfil_detection is an exact prefilter in the same way. A span
+    with no backslash and no non-ASCII byte holds every string value
+    verbatim between quotes, and '"' is in neither the base64 nor the hex
+    alphabet, so every run the plugin can see is present byte for byte in
+    the raw span, with the same length, decoded bytes, printable count and
+    keyword mask — all integers, computed by exfil.hip exactly as by
+    ops/exfil.py, so nothing is subtracted. The prefilter over-flags only
+    where the raw span has runs the plugin never scans (keys, long
+    integers); it never under-flags. Flagged rows, and every span with a
+    backslash or a non-ASCII byte, run the exact CPU plugin
+    (tests/test_exfil_plugin.py checks the containment on the CPU).
 """
 
 from __future__ import annotations
@@ -145,7 +156,7 @@ class GpuPluginPipeline:
         self.deny, self.harm, self.pii, self.regex = h.deny, h.harm, h.pii, h.regex
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
-        self.toon, self.out_guard, self.secrets = h.toon, h.out_guard, h.secrets
+        self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -179,6 +190,15 @@ class GpuPluginPipeline:
                 # backslash / non-ASCII bit, which the prefilter needs
                 self._secret_tabs = [(hip.entropy_table(np.full(256, 0xFF, dtype=np.uint8), device),
                                       float("inf"))]
+
+        # encoded_exfil_detection: its keyword tables plus one symbol table
+        # and symbol width per configured encoding (exfil.hip)
+        self._exfil_kw: Optional[hip.DeviceScanTables] = None
+        self._exfil_tabs: List[Tuple[torch.Tensor, int]] = []
+        if self.exfil is not None:
+            self._exfil_kw = hip.DeviceScanTables(self.exfil.keyword_tables(), device)
+            self._exfil_tabs = [(hip.entropy_table(tab, device), bits)
+                                for (_e, _c, tab, bits) in self.exfil.detectors]
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -238,12 +258,13 @@ class GpuPluginPipeline:
 
         # fused multi-bank scans: pass 3's bank set is static; pass 1's holds
         # the per-registry schema bank and lives in the ToolTable. With secrets
-        # on, pass 3 stays eager: token_entropy runs on the same uploaded tensors
+        # or exfil on, pass 3 stays eager: token_entropy / decode_scan run on
+        # the same uploaded tensors
         self._bankset3 = hip.ScanBankSet(
             [(n, self.banks[n]) for n in ("pii", "regex", "harm", "postmeta", "secrets")
              if n in self.banks],
             device)
-        self._graphs3 = Pass3Graphs(self) if self.secrets is None else None
+        self._graphs3 = Pass3Graphs(self) if self.secrets is None and self.exfil is None else None
 
         # native decision-plane stores + string tables (fastpath.cpp)
         self._slot_store = hip.store_new(self.semcache.capacity) if self.semcache is not None else 0
@@ -266,6 +287,7 @@ class GpuPluginPipeline:
         self.post_c_punt = 0  # rows the C post lane punted back to Python
         self.host_bound = 0   # requests routed to the CPU chain by plugin bindings
         self.secrets_routed = 0  # requests the secrets prefilter sent to the CPU chain
+        self.exfil_routed = 0    # requests the encoded-exfil prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         self.timing_enabled = bool(os.environ.get("FORGE_PIPELINE_TIMING"))
         self.timing: Dict[str, float] = {}
@@ -396,7 +418,8 @@ class GpuPluginPipeline:
                     args_b, args_e, blob, env, responses, tools, self)
 
         fw_state = self._forward_foreign(rs, raws, user, users)
-        if len(rs) and (tools.hostbound is not None or tools.secrets is not None):
+        if len(rs) and (tools.hostbound is not None or tools.secrets is not None
+                        or tools.exfil is not None):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -455,17 +478,28 @@ class GpuPluginPipeline:
         if tools.hostbound is not None:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
-        if tools.secrets is not None:
-            # secrets_detection pre-pass: rows of secrets-active tools
-            # whose raw argument bytes MAY hold a secret leave with the
-            # host-bound rows and run the exact CPU chain, plugin included
-            sec_rows = np.zeros(m, dtype=bool)
-            sec_rows[valid] = tools.secrets[tool_idx[valid]]
-            sec_rows &= ~hb_mask
-            if sec_rows.any():
-                flagged = await self._secrets_prepass(rs.blob, rs.args_b, rs.args_e, sec_rows)
-                self.secrets_routed += int(flagged.sum())
-                hb_mask |= flagged
+        # secrets_detection / encoded_exfil_detection pre-pass: rows of
+        # tools either plugin is active for, whose raw argument bytes MAY
+        # hold a finding, leave with the host-bound rows and run the exact
+        # CPU chain, plugins included
+        def plugin_rows(per_tool: Optional[np.ndarray]) -> Optional[np.ndarray]:
+            if per_tool is None:
+                return None
+            rows = np.zeros(m, dtype=bool)
+            rows[valid] = per_tool[tool_idx[valid]]
+            rows &= ~hb_mask
+            return rows if rows.any() else None
+
+        sec_rows, exf_rows = plugin_rows(tools.secrets), plugin_rows(tools.exfil)
+        if sec_rows is not None or exf_rows is not None:
+            sec_flagged, exf_flagged = await self._raw_prepass(rs.blob, rs.args_b, rs.args_e,
+                                                               sec_rows, exf_rows)
+            if sec_flagged is not None:
+                self.secrets_routed += int(sec_flagged.sum())
+                hb_mask |= sec_flagged
+            if exf_flagged is not None:
+                self.exfil_routed += int(exf_flagged.sum())
+                hb_mask |= exf_flagged
         if hb_mask.any():
             self.host_bound += n_bound
             await self._host_chain_rows(rs.rows[hb_mask], raws, row_user, server_id, rs.responses)
@@ -748,32 +782,70 @@ class GpuPluginPipeline:
             out |= (flags.cpu().numpy() & 1) != 0
         return out
 
-    async def _secrets_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
-                               sec_rows: np.ndarray) -> np.ndarray:
-        """secrets_detection prefilter over raw argument bytes → bool[m],
-        True where the row must run the exact CPU chain. Eager, under
-        _gpu_lock: the format bank (scan.hip) and one token_entropy launch
-        per configured alphabet over the secrets-active rows; every other
-        row gets an empty span. The blob is uploaded here and again by pass
-        1 on purpose — folding this pre-pass into the captured pass-1 graph
-        is a later change."""
+    def _exfil_launch(self, data_t, beg_t, end_t):
+        """One decode_scan launch per configured encoding → [(counts, kw, span, flags)]."""
+        p = self.exfil
+        return [hip.decode_scan(data_t, beg_t, end_t, tab, bits, p.min_len,
+                                p.min_printable_permille, self._exfil_kw)
+                for tab, bits in self._exfil_tabs]
+
+    def _exfil_flags(self, dec, n: int) -> np.ndarray:
+        """Encoded-exfil prefilter over hip.decode_scan outputs, one entry
+        per encoding: a row is flagged when a text run holds a keyword
+        (any text run when the plugin does not require one), or when its
+        span holds a backslash or a non-ASCII byte. Integer outputs, equal
+        to the plugin's own: nothing to round."""
+        out = np.zeros(n, dtype=bool)
+        for counts, _kw, _span, flags in dec:
+            c = counts.cpu().numpy()
+            out |= c[:, 2] > 0
+            if not self.exfil.require_keyword:
+                out |= c[:, 1] > 0
+            out |= (flags.cpu().numpy() & 1) != 0
+        return out
+
+    async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
+                           sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray]
+                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """secrets_detection and encoded_exfil_detection prefilters over raw
+        argument bytes → (bool[m] or None) per plugin, True where the row
+        must run the exact CPU chain; `sec_rows` / `exf_rows` mark the rows
+        of tools each plugin is active for (None: not this batch). Eager,
+        under _gpu_lock, ONE upload for both: the secrets format bank
+        (scan.hip) and one token_entropy launch per alphabet, one decode_scan
+        launch per encoding, over the union of the marked rows; every other
+        row gets an empty span, and each verdict is masked with its own
+        plugin's rows. The blob is uploaded here and again by pass 1 on
+        purpose — folding this pre-pass into the captured pass-1 graph is a
+        later change. Timed as gp0_secrets when secrets_detection takes
+        part, as gp0_exfil when only encoded_exfil_detection does."""
         t0 = self._tic()
         m = args_b.shape[0]
-        sb = np.ascontiguousarray(np.where(sec_rows, args_b, 0).astype(np.int32))
-        se = np.ascontiguousarray(np.where(sec_rows, args_e, 0).astype(np.int32))
+        rows = sec_rows if exf_rows is None else exf_rows if sec_rows is None else sec_rows | exf_rows
+        sb = np.ascontiguousarray(np.where(rows, args_b, 0).astype(np.int32))
+        se = np.ascontiguousarray(np.where(rows, args_e, 0).astype(np.int32))
 
         def launch(data_t, beg_t, end_t):
-            mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0] \
-                if "secrets" in self.banks else None
-            return mask_t, self._entropy_launch(data_t, beg_t, end_t)
+            mask_t = ent = dec = None
+            if sec_rows is not None:
+                if "secrets" in self.banks:
+                    mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0]
+                ent = self._entropy_launch(data_t, beg_t, end_t)
+            if exf_rows is not None:
+                dec = self._exfil_launch(data_t, beg_t, end_t)
+            return mask_t, ent, dec
 
-        _mm, _scores, (mask_t, ent) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        flagged = self._entropy_flags(ent, m)
-        if mask_t is not None:
-            flagged |= mask_t.cpu().numpy() != 0
-        flagged &= sec_rows
-        self._toc("gp0_secrets", t0)
-        return flagged
+        _mm, _scores, (mask_t, ent, dec) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
+        sec_flagged = exf_flagged = None
+        if sec_rows is not None:
+            sec_flagged = self._entropy_flags(ent, m)
+            if mask_t is not None:
+                sec_flagged |= mask_t.cpu().numpy() != 0
+            sec_flagged &= sec_rows
+        if exf_rows is not None:
+            exf_flagged = self._exfil_flags(dec, m) & exf_rows
+        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil", t0)
+        return sec_flagged, exf_flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1222,16 +1294,24 @@ class GpuPluginPipeline:
         toon_meta = np.zeros(n_all, dtype=bool)
         regex3 = np.zeros(n_all, dtype=bool)
         sec3 = None  # secrets prefilter verdict per result (secrets-active tools only)
+        exf3 = None  # encoded-exfil prefilter verdict per result (exfil-active tools only)
         if n_all:
-            mm3, _scores, ent3 = await self._scan_pass(
+            def pass3_extra(data_t, beg_t, end_t):
+                return (self._entropy_launch(data_t, beg_t, end_t) if self.secrets is not None else None,
+                        self._exfil_launch(data_t, beg_t, end_t) if self.exfil is not None else None)
+
+            mm3, _scores, ext3 = await self._scan_pass(
                 self._graphs3, self._bankset3, res_blob,
                 res_beg.astype(np.int32), res_end.astype(np.int32), n_all,
-                extra=self._entropy_launch if self.secrets is not None else None)
+                extra=pass3_extra if self._graphs3 is None else None)
+            ent3, dec3 = ext3 or (None, None)
             if self.secrets is not None and tools.secrets is not None:
                 sec3 = self._entropy_flags(ent3, n_all)
                 if "secrets" in self._bankset3.index:
                     sec3 |= mm3[self._bankset3.index["secrets"]] != 0
                 sec3 &= tools.secrets[np.clip(rs.tool_idx[all_js_np], 0, None)]
+            if self.exfil is not None and tools.exfil is not None:
+                exf3 = self._exfil_flags(dec3, n_all) & tools.exfil[np.clip(rs.tool_idx[all_js_np], 0, None)]
             for b, i in self._bankset3.index.items():
                 h = mm3[i] != 0
                 if b == "postmeta":
@@ -1249,6 +1329,8 @@ class GpuPluginPipeline:
             (res_len > guard_max) | err_rows.astype(bool)
         if sec3 is not None:
             needs_host = needs_host | sec3
+        if exf3 is not None:
+            needs_host = needs_host | exf3
         return needs_host, regex3
 
     def _host_post_rows(self, rs: RowSet, all_js, all_js_np, host_ks, regex3, res_blob, res_beg, res_end,
@@ -1387,7 +1469,7 @@ class GpuPluginPipeline:
             st["results"] = []
 
     def _host_post(self, mt: _ToolMeta, rb: bytes) -> Tuple[bytes, bool, Optional[str]]:
-        """Exact host post chain for flagged results: secrets(5) → regex(20) → pii(30) →
+        """Exact host post chain for flagged results: secrets(5) → exfil(6) → regex(20) → pii(30) →
         output-schema → harm(60) → toon(900) → guard(950)."""
         self.post_rewrites += 1
         try:
@@ -1408,6 +1490,15 @@ class GpuPluginPipeline:
                     PluginMode.ENFORCE, PluginMode.ENFORCE_IGNORE_ERROR):
                 return rb, True, f"secrets_detection: {reason}"
             if findings and self.secrets.action == "redact":
+                result = new
+        if self._active(self.exfil, name, block_class=False):
+            # encoded_exfil_detection(6) next, with the same mode handling
+            new, findings = self.exfil.scan_payload(result)
+            reason = self.exfil.block_reason(findings)
+            if reason is not None and self.engine.plugins.effective_mode(self.exfil, name) in (
+                    PluginMode.ENFORCE, PluginMode.ENFORCE_IGNORE_ERROR):
+                return rb, True, f"encoded_exfil_detection: {reason}"
+            if findings and self.exfil.action == "redact":
                 result = new
         if self._active(self.regex, name, block_class=False):
             result = _walk_strings(result, self.regex.apply_rules)
@@ -1448,6 +1539,7 @@ class GpuPluginPipeline:
             "batches": self.batches, "requests": self.requests, "fast_path": self.fast_path,
             "slow_path": self.slow_path, "blocked": self.blocked, "cache_hits": self.cache_hits,
             "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
+            "exfil_routed": self.exfil_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "banks": {k: {"states": v.n_states, "classes": v.n_classes} for k, v in self.banks.items()},

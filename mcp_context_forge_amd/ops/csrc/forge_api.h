@@ -20,12 +20,20 @@
 #define FORGE_ERR_ACT 9002        /* unknown activation code */
 #define FORGE_ERR_GEMV_K 9003     /* gemv_head needs K % 512 == 0 */
 #define FORGE_ERR_ROW_ALIGN 9004  /* row length must be a multiple of 8 bf16 */
+#define FORGE_ERR_DECODE_SCAN 9005  /* decode_scan: bits, kw_max_len or keyword table size */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
 #define FORGE_SCAN_LDS_LIMIT (64 * 1024)
 #define FORGE_SCAN_TABLE_BYTES(n_states, n_classes) \
     ((int64_t)(n_states) * (n_classes) * 2 + 256 + (int64_t)(n_states) * 4)
+
+/* forge_decode_scan always stages its keyword tables into LDS: tables over
+ * this many FORGE_SCAN_TABLE_BYTES, or a longest keyword over
+ * FORGE_DECODE_SCAN_KW_MAX_LEN, are an argument error. ops/hip.py carries the
+ * limit as DECODE_SCAN_TABLE_LIMIT. */
+#define FORGE_DECODE_SCAN_TABLE_LIMIT (16 * 1024)
+#define FORGE_DECODE_SCAN_KW_MAX_LEN 16
 
 typedef void (*forge_task_fn)(int index, void* ctx);
 
@@ -51,6 +59,19 @@ int forge_token_entropy(const void* data, const void* beg, const void* end_, int
                         const void* sym, int min_len,
                         void* out_h, void* out_span, void* out_runs, void* out_flags,
                         void* stream);
+
+/* One wave per request: decode the in-alphabet runs of at least min_len bytes
+ * (bits per symbol 4 or 6, MSB first), call a run text when
+ * printable * 1000 >= min_printable_permille * dec_len, and match the keyword
+ * DFA (next / klass / accept, longest keyword kw_max_len) over the decoded
+ * bytes of text runs. out_counts i32[batch][3] (qualifying, text, text with a
+ * keyword), out_kw u32[batch], out_span i32[batch][2], out_flags i32[batch]. */
+int forge_decode_scan(const void* data, const void* beg, const void* end_, int batch,
+                      const void* sym, int bits, int min_len, int min_printable_permille,
+                      const void* next, const void* klass, const void* accept,
+                      int n_states, int n_classes, int kw_max_len,
+                      void* out_counts, void* out_kw, void* out_span, void* out_flags,
+                      void* stream);
 
 int forge_featurize(const void* data, const void* beg, const void* end_, int batch, int dim,
                     void* out_bf16, void* out_f32, void* stream);

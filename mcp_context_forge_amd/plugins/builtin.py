@@ -7,7 +7,10 @@ Per-plugin reference analogs (behavioral port, no code copied):
   secrets_detection  → plugins/secrets_detection (provider key formats + high-entropy
                        base64/hex tokens; block / redact / audit). Opt-in: not
                        in the default chain
-  schema_guard       → plugins/schema_guard (JSON-Schema arg/result validation)
+  encoded_exfil_detection → cpex-encoded-exfil-detection (long base64/hex runs that
+                       decode to printable text naming a credential; block /
+                       redact / audit). Opt-in: not in the default chain
+  schema_guard      → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
   harmful_content    → plugins/harmful_content_detector (keyword+classifier)
@@ -349,6 +352,110 @@ class SecretsDetectionPlugin(Plugin):
         if self.action == "redact":
             return PluginResult.ok(new_payload, secrets=sorted(set(findings)))
         return PluginResult.ok(secrets=sorted(set(findings)))  # audit: annotate only
+
+    tool_pre_invoke = _apply
+    tool_post_invoke = _apply
+    prompt_pre_fetch = _apply
+    resource_post_fetch = _apply
+
+
+class EncodedExfilDetectionPlugin(Plugin):
+    """Stop credentials that travel ENCODED: a long base64 or hex run whose
+    decoded bytes are mostly printable text and name a credential
+    (ops/exfil.py; exfil.hip on the GPU path). The encoded bytes pass every
+    byte-pattern plugin and, being encoded English, the entropy detector too.
+    Priority 6: directly after secrets_detection and before any rewriter in
+    both directions, which is what makes the pipeline's raw-byte prefilter
+    sound.
+
+    Config: action block (default, code "exfil") | redact | audit,
+    redaction_text, min_findings_to_block, encodings (["base64", "hex"]),
+    min_len (24), min_printable (0.8, kept as integer per-mille), keywords
+    (1 to 32 words of 2 to 16 printable ASCII bytes, matched case-
+    insensitively), require_keyword (true: a finding is a text run that
+    holds a keyword; false: any text run).
+    """
+
+    name = "encoded_exfil_detection"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.TOOL_POST_INVOKE, HookType.PROMPT_PRE_FETCH,
+             HookType.RESOURCE_POST_FETCH)
+    priority = 6
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import exfil as _exfil
+
+        self._exfil = _exfil
+        self.action: str = self.config.get("action", "block")  # block | redact | audit
+        self.redaction_text: str = str(self.config.get("redaction_text", "[ENCODED_REDACTED]"))
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self.min_len = max(int(self.config.get("min_len", 24)), 1)
+        self.min_printable_permille = int(round(float(self.config.get("min_printable", 0.8)) * 1000))
+        self.require_keyword = bool(self.config.get("require_keyword", True))
+        encodings = list(self.config.get("encodings") or ["base64", "hex"])
+        for e in encodings:
+            if e not in _exfil.ENCODINGS:
+                raise ValueError(f"unknown encoding {e!r}")
+        self.keywords: List[str] = list(self.config.get("keywords") or _exfil.DEFAULT_KEYWORDS)
+        self._kw_tables = _exfil.compile_keywords(self.keywords)   # raises over the kernel's limits
+        # (encoding, category, symbol table, bits per symbol) per configured encoding
+        self.detectors = [(e, f"encoded_{e}", _exfil.ENCODINGS[e][0](), _exfil.ENCODINGS[e][1])
+                          for e in encodings]
+
+    def keyword_tables(self) -> dfa.ScanTables:
+        return self._kw_tables
+
+    def find_spans(self, raw: bytes) -> List[Tuple[int, int, str]]:
+        """Every finding in one string's UTF-8 bytes as (beg, end, category)."""
+        out: List[Tuple[int, int, str]] = []
+        for _e, cat, table, bits in self.detectors:
+            runs = self._exfil.decode_scan_reference(raw, table, bits, self.min_len,
+                                                     self.min_printable_permille, self._kw_tables)[0]
+            out.extend((b, b + n, cat) for (b, n, _dl, _pr, text, mask) in runs
+                       if text and (mask or not self.require_keyword))
+        return out
+
+    _redact = SecretsDetectionPlugin._redact   # overlapping spans collapse to one replacement
+
+    def scan_payload(self, payload: Any) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value, shared by the hooks and
+        the GPU pipeline's host lane, like SecretsDetectionPlugin.scan_payload.
+        → (payload, findings): the payload has every finding's span replaced
+        by redaction_text when action is "redact" (otherwise it is returned
+        as is); findings holds one category name per finding."""
+        findings: List[str] = []
+        redact = self.action == "redact"
+
+        def fn(s: str) -> str:
+            raw = s.encode("utf-8", "surrogatepass")
+            spans = self.find_spans(raw)
+            if not spans:
+                return s
+            findings.extend(c for _b, _e, c in spans)
+            if not redact:
+                return s
+            return self._redact(raw, spans).decode("utf-8", "surrogatepass")
+
+        new_payload = _walk_strings(payload, fn)
+        return (new_payload if redact and findings else payload), findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"encoded payloads detected: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        new_payload, findings = self.scan_payload(ctx.args)
+        if not findings:
+            return PluginResult.ok()
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="exfil")
+        if self.action == "redact":
+            return PluginResult.ok(new_payload, encoded=sorted(set(findings)))
+        return PluginResult.ok(encoded=sorted(set(findings)))  # audit: annotate only
 
     tool_pre_invoke = _apply
     tool_post_invoke = _apply
@@ -748,6 +855,7 @@ BUILTIN_PLUGINS = {
         RegexFilterPlugin,
         PIIFilterPlugin,
         SecretsDetectionPlugin,
+        EncodedExfilDetectionPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
