@@ -60,7 +60,20 @@ chain):
     where the raw span has runs the plugin never scans (keys, long
     integers); it never under-flags. Flagged rows, and every span with a
     backslash or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_exfil_plugin.py checks the containment on the CPU).
+    (tests/test_exfil_plugin.py checks the containment on the CPU);
+  * sql_sanitizer is an exact prefilter in the same way. A span with no
+    backslash and no non-ASCII byte holds every string value verbatim
+    between quotes, and no such value contains '"'. sql.hip scans the raw
+    span in boundary mode, where every '"' resets the lexer to CODE and
+    closes the statement, so each value is lexed, matched and folded from
+    a fresh state exactly as the plugin scans it alone in text mode, and
+    the per-span counts are sums (the blocked mask an OR) over the values
+    plus whatever keys and bare literals add: they can only add findings.
+    All outputs are integers, computed by sql.hip exactly as by ops/sql.py.
+    Rows with a delete / update without where the plugin blocks, a blocked
+    word, a comment when strip_comments is on, and every span with a
+    backslash or a non-ASCII byte, run the exact CPU plugin
+    (tests/test_sql_plugin.py checks the containment on the CPU).
 """
 
 from __future__ import annotations
@@ -157,6 +170,7 @@ class GpuPluginPipeline:
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
         self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
+        self.sql = h.sql
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -199,6 +213,13 @@ class GpuPluginPipeline:
             self._exfil_kw = hip.DeviceScanTables(self.exfil.keyword_tables(), device)
             self._exfil_tabs = [(hip.entropy_table(tab, device), bits)
                                 for (_e, _c, tab, bits) in self.exfil.detectors]
+
+        # sql_sanitizer: its keyword tables and the keyword lengths (sql.hip)
+        self._sql_kw: Optional[hip.DeviceScanTables] = None
+        self._sql_kw_len: Optional[torch.Tensor] = None
+        if self.sql is not None:
+            self._sql_kw = hip.DeviceScanTables(self.sql.keyword_tables(), device)
+            self._sql_kw_len = torch.tensor(self.sql.keyword_lengths(), dtype=torch.int32, device=device)
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -288,6 +309,7 @@ class GpuPluginPipeline:
         self.host_bound = 0   # requests routed to the CPU chain by plugin bindings
         self.secrets_routed = 0  # requests the secrets prefilter sent to the CPU chain
         self.exfil_routed = 0    # requests the encoded-exfil prefilter sent to the CPU chain
+        self.sql_routed = 0      # requests the sql prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         self.timing_enabled = bool(os.environ.get("FORGE_PIPELINE_TIMING"))
         self.timing: Dict[str, float] = {}
@@ -419,7 +441,7 @@ class GpuPluginPipeline:
 
         fw_state = self._forward_foreign(rs, raws, user, users)
         if len(rs) and (tools.hostbound is not None or tools.secrets is not None
-                        or tools.exfil is not None):
+                        or tools.exfil is not None or tools.sql is not None):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -478,8 +500,8 @@ class GpuPluginPipeline:
         if tools.hostbound is not None:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
-        # secrets_detection / encoded_exfil_detection pre-pass: rows of
-        # tools either plugin is active for, whose raw argument bytes MAY
+        # secrets_detection / encoded_exfil_detection / sql_sanitizer pre-pass:
+        # rows of tools one of them is active for, whose raw argument bytes MAY
         # hold a finding, leave with the host-bound rows and run the exact
         # CPU chain, plugins included
         def plugin_rows(per_tool: Optional[np.ndarray]) -> Optional[np.ndarray]:
@@ -491,15 +513,19 @@ class GpuPluginPipeline:
             return rows if rows.any() else None
 
         sec_rows, exf_rows = plugin_rows(tools.secrets), plugin_rows(tools.exfil)
-        if sec_rows is not None or exf_rows is not None:
-            sec_flagged, exf_flagged = await self._raw_prepass(rs.blob, rs.args_b, rs.args_e,
-                                                               sec_rows, exf_rows)
+        sql_rows = plugin_rows(tools.sql)
+        if sec_rows is not None or exf_rows is not None or sql_rows is not None:
+            sec_flagged, exf_flagged, sql_flagged = await self._raw_prepass(
+                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows)
             if sec_flagged is not None:
                 self.secrets_routed += int(sec_flagged.sum())
                 hb_mask |= sec_flagged
             if exf_flagged is not None:
                 self.exfil_routed += int(exf_flagged.sum())
                 hb_mask |= exf_flagged
+            if sql_flagged is not None:
+                self.sql_routed += int(sql_flagged.sum())
+                hb_mask |= sql_flagged
         if hb_mask.any():
             self.host_bound += n_bound
             await self._host_chain_rows(rs.rows[hb_mask], raws, row_user, server_id, rs.responses)
@@ -804,39 +830,65 @@ class GpuPluginPipeline:
             out |= (flags.cpu().numpy() & 1) != 0
         return out
 
+    def _sql_flags(self, out, n: int) -> np.ndarray:
+        """SQL prefilter over hip.sql_scan outputs (boundary mode): a row is
+        flagged when it holds a delete / update without where that the
+        plugin blocks, a blocked word, a comment while strip_comments is on,
+        or when its span holds a backslash or a non-ASCII byte. Integer
+        outputs, equal to the plugin's own: nothing to round."""
+        counts, blocked, _first, flags = out
+        c = counts.cpu().numpy()
+        res = blocked.cpu().numpy() != 0
+        if self.sql.block_delete_without_where:
+            res |= c[:, 1] > 0
+        if self.sql.block_update_without_where:
+            res |= c[:, 2] > 0
+        if self.sql.strip_comments:
+            res |= c[:, 3] > 0
+        res |= (flags.cpu().numpy() & 1) != 0
+        return res
+
     async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
-                           sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray]
-                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
-        """secrets_detection and encoded_exfil_detection prefilters over raw
-        argument bytes → (bool[m] or None) per plugin, True where the row
-        must run the exact CPU chain; `sec_rows` / `exf_rows` mark the rows
-        of tools each plugin is active for (None: not this batch). Eager,
-        under _gpu_lock, ONE upload for both: the secrets format bank
-        (scan.hip) and one token_entropy launch per alphabet, one decode_scan
-        launch per encoding, over the union of the marked rows; every other
-        row gets an empty span, and each verdict is masked with its own
-        plugin's rows. The blob is uploaded here and again by pass 1 on
+                           sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray],
+                           sql_rows: Optional[np.ndarray] = None
+                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
+        """secrets_detection, encoded_exfil_detection and sql_sanitizer
+        prefilters over raw argument bytes → (bool[m] or None) per plugin,
+        True where the row must run the exact CPU chain; `sec_rows` /
+        `exf_rows` / `sql_rows` mark the rows of tools each plugin is active
+        for (None: not this batch). Eager, under _gpu_lock, ONE upload for
+        all: the secrets format bank (scan.hip) and one token_entropy launch
+        per alphabet, one decode_scan launch per encoding, one sql_scan
+        launch in boundary mode, over the union of the marked rows; every
+        other row gets an empty span, and each verdict is masked with its
+        own plugin's rows. The blob is uploaded here and again by pass 1 on
         purpose — folding this pre-pass into the captured pass-1 graph is a
         later change. Timed as gp0_secrets when secrets_detection takes
-        part, as gp0_exfil when only encoded_exfil_detection does."""
+        part, else as gp0_exfil when encoded_exfil_detection does, as
+        gp0_sql when sql_sanitizer alone does."""
         t0 = self._tic()
         m = args_b.shape[0]
-        rows = sec_rows if exf_rows is None else exf_rows if sec_rows is None else sec_rows | exf_rows
+        rows = np.zeros(m, dtype=bool)
+        for part in (sec_rows, exf_rows, sql_rows):
+            if part is not None:
+                rows |= part
         sb = np.ascontiguousarray(np.where(rows, args_b, 0).astype(np.int32))
         se = np.ascontiguousarray(np.where(rows, args_e, 0).astype(np.int32))
 
         def launch(data_t, beg_t, end_t):
-            mask_t = ent = dec = None
+            mask_t = ent = dec = sq = None
             if sec_rows is not None:
                 if "secrets" in self.banks:
                     mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0]
                 ent = self._entropy_launch(data_t, beg_t, end_t)
             if exf_rows is not None:
                 dec = self._exfil_launch(data_t, beg_t, end_t)
-            return mask_t, ent, dec
+            if sql_rows is not None:
+                sq = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
+            return mask_t, ent, dec, sq
 
-        _mm, _scores, (mask_t, ent, dec) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        sec_flagged = exf_flagged = None
+        _mm, _scores, (mask_t, ent, dec, sq) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
+        sec_flagged = exf_flagged = sql_flagged = None
         if sec_rows is not None:
             sec_flagged = self._entropy_flags(ent, m)
             if mask_t is not None:
@@ -844,8 +896,10 @@ class GpuPluginPipeline:
             sec_flagged &= sec_rows
         if exf_rows is not None:
             exf_flagged = self._exfil_flags(dec, m) & exf_rows
-        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil", t0)
-        return sec_flagged, exf_flagged
+        if sql_rows is not None:
+            sql_flagged = self._sql_flags(sq, m) & sql_rows
+        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil" if exf_rows is not None else "gp0_sql", t0)
+        return sec_flagged, exf_flagged, sql_flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1540,6 +1594,7 @@ class GpuPluginPipeline:
             "slow_path": self.slow_path, "blocked": self.blocked, "cache_hits": self.cache_hits,
             "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
             "exfil_routed": self.exfil_routed,
+            "sql_routed": self.sql_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "banks": {k: {"states": v.n_states, "classes": v.n_classes} for k, v in self.banks.items()},

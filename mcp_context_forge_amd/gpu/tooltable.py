@@ -41,7 +41,7 @@ _HANDLES = {"deny": "deny_filter", "harm": "harmful_content_detector", "pii": "p
             "schema_guard": "schema_guard", "toon": "toon_encoder",
             "out_guard": "output_length_guard", "exact_cache": "cached_tool_result",
             "breaker": "circuit_breaker", "secrets": "secrets_detection",
-            "exfil": "encoded_exfil_detection"}
+            "exfil": "encoded_exfil_detection", "sql": "sql_sanitizer"}
 MODELED = frozenset(_HANDLES.values())
 
 
@@ -116,14 +116,14 @@ class _ToolMeta:
 class ToolTable:
     """One registry/plugin generation's tables. Arrays are indexed by the
     `tool_idx` that `toolmap` resolves; with no tools they hold one dummy
-    entry. `hostbound`, `secrets`, `exfil`, `sk_tables`, `schema_bank` and
+    entry. `hostbound`, `secrets`, `exfil`, `sql`, `sk_tables`, `schema_bank` and
     `graphs` are None where absent."""
 
     __slots__ = ("generation", "plugins_ver", "metas", "by_name", "index", "names", "tids",
                  "schema_bank", "nest_bits", "bankset1", "graphs", "toolmap",
                  "name_blob", "name_beg", "name_end", "required", "typed", "native_kind",
                  "outschema", "thash", "semallow",
-                 "flags", "postlane", "hostbound", "secrets", "exfil",
+                 "flags", "postlane", "hostbound", "secrets", "exfil", "sql",
                  "rw_norm", "rw_regex", "rw_deny", "rw_pii", "rw_harm", "mod_app",
                  "sk_tables", "sk_range")
 
@@ -300,7 +300,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     `bank_names` are the content banks that exist (only "regex" is asked)."""
     n1 = max(len(metas), 1)
     modeled_banks = {p.name for p in (h.deny, h.pii, h.regex, h.normalizer, h.moderation, h.harm,
-                                      h.schema_guard, h.secrets, h.exfil) if p is not None}
+                                      h.schema_guard, h.secrets, h.exfil, h.sql) if p is not None}
     extra_chain = [p for p in mgr.plugins
                    if p.mode != PluginMode.DISABLED and p.name not in MODELED
                    and (HookType.TOOL_PRE_INVOKE in p.hooks or HookType.TOOL_POST_INVOKE in p.hooks)]
@@ -309,8 +309,8 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     postlane = np.full(n1, -1, dtype=np.int8)
     # rewrite/verdict lane per-tool activation (hoists the per-row
     # active/applies python calls out of the hot loops)
-    t.rw_norm, t.rw_regex, t.rw_deny, t.rw_pii, t.rw_harm, t.mod_app, sec_act, exf_act, t.semallow = (
-        np.zeros(n1, dtype=bool) for _ in range(9))
+    (t.rw_norm, t.rw_regex, t.rw_deny, t.rw_pii, t.rw_harm, t.mod_app, sec_act, exf_act, sql_act,
+     t.semallow) = (np.zeros(n1, dtype=bool) for _ in range(10))
     for i, m in enumerate(metas):
         name = m.name
         m.host_chain = any(b.get("config") or (pname not in modeled_banks)
@@ -330,6 +330,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
         t.mod_app[i] = applies(h.moderation, name)
         sec_act[i] = active(mgr, h.secrets, name, block_class=False)
         exf_act[i] = active(mgr, h.exfil, name, block_class=False)
+        sql_act[i] = active(mgr, h.sql, name, block_class=False)
         # semcache insert allowlist (tool-level; lookups are gated by TF_CACHE)
         t.semallow[i] = bool(semcache_on and h.semcache_plugin.cacheable(name))
         # TF_NORM = "escape triggers route this tool to the host path":
@@ -375,6 +376,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     t.hostbound = hostbound if hostbound.any() else None
     t.secrets = sec_act if sec_act.any() else None
     t.exfil = exf_act if exf_act.any() else None
+    t.sql = sql_act if sql_act.any() else None
 
 
 # ---- schema-key tables ----

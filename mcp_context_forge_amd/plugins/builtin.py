@@ -10,6 +10,10 @@ Per-plugin reference analogs (behavioral port, no code copied):
   encoded_exfil_detection → cpex-encoded-exfil-detection (long base64/hex runs that
                        decode to printable text naming a credential; block /
                        redact / audit). Opt-in: not in the default chain
+  sql_sanitizer      → plugins/sql_sanitizer (blocked statement keywords, DELETE /
+                       UPDATE without WHERE, outside strings and comments;
+                       block / audit, optional comment stripping). Opt-in: not
+                       in the default chain
   schema_guard      → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
@@ -463,6 +467,123 @@ class EncodedExfilDetectionPlugin(Plugin):
     resource_post_fetch = _apply
 
 
+class SqlSanitizerPlugin(Plugin):
+    """Stop dangerous SQL travelling in arguments: blocked statement keywords
+    (DROP, TRUNCATE, ...) and DELETE / UPDATE without WHERE, found by a lexer
+    that knows string literals and comments and folds per statement
+    (ops/sql.py; sql.hip on the GPU path). A keyword inside a string or a
+    comment is not code, `DR/**/OP` is two words, `drops` is not `drop`.
+    Priority 7: after encoded_exfil_detection and before any rewriter, which
+    is what makes the pipeline's raw-byte prefilter sound. Pre hooks only, as
+    the reference plugin.
+
+    Config: action block (default, code "sql") | audit, blocked_statements
+    (1 to 24 words of 2 to 16 bytes over [A-Za-z0-9_], matched as whole words
+    and case-insensitively; default drop, truncate, alter, grant, revoke),
+    block_delete_without_where (true), block_update_without_where (true),
+    min_findings_to_block (1), fields (top-level argument names to scan;
+    default every string value), strip_comments (false: when true every
+    comment of a scanned string becomes one space in the forwarded payload,
+    unless the request is blocked).
+
+    Dialect limits: backticks, [..] identifiers, # comments, dollar quoting
+    and backslash escapes are not lexed; those bytes are plain code bytes.
+    """
+
+    name = "sql_sanitizer"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.PROMPT_PRE_FETCH)
+    priority = 7
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import sql as _sql
+
+        self._sql = _sql
+        self.action: str = self.config.get("action", "block")  # block | audit
+        if self.action not in ("block", "audit"):
+            raise ValueError(f"unknown sql_sanitizer action {self.action!r}")
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self.block_delete_without_where = bool(self.config.get("block_delete_without_where", True))
+        self.block_update_without_where = bool(self.config.get("block_update_without_where", True))
+        self.strip_comments = bool(self.config.get("strip_comments", False))
+        fields = self.config.get("fields")
+        self.fields: Optional[List[str]] = [str(f) for f in fields] if fields else None
+        self.blocked: List[str] = list(self.config.get("blocked_statements") or _sql.DEFAULT_BLOCKED)
+        self._kw_tables, self._kw_len = _sql.compile_sql_keywords(self.blocked)   # raises over the kernel's limits
+
+    def keyword_tables(self) -> dfa.ScanTables:
+        return self._kw_tables
+
+    def keyword_lengths(self) -> List[int]:
+        return list(self._kw_len)
+
+    def _wanted(self, category: str) -> bool:
+        if category == "delete_without_where":
+            return self.block_delete_without_where
+        if category == "update_without_where":
+            return self.block_update_without_where
+        return True
+
+    def _scan(self, raw: bytes) -> Tuple[List[Tuple[int, int, str]], List[Tuple[int, int]]]:
+        findings, comments = self._sql.sql_scan_reference(raw, self._kw_tables, self._kw_len, False)[:2]
+        return [(b, b + n, c) for (b, n, c) in findings if self._wanted(c)], comments
+
+    def find_spans(self, raw: bytes) -> List[Tuple[int, int, str]]:
+        """Every finding in one string's UTF-8 bytes as (beg, end, category)."""
+        return self._scan(raw)[0]
+
+    def scan_payload(self, payload: Any) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value (of the `fields` arguments
+        when configured). → (payload, findings): the payload has every
+        comment replaced by one space when strip_comments is on and a scanned
+        string held one (otherwise it is returned as is); findings holds one
+        category name per finding."""
+        findings: List[str] = []
+        stripped = False
+
+        def fn(s: str) -> str:
+            nonlocal stripped
+            raw = s.encode("utf-8", "surrogatepass")
+            spans, comments = self._scan(raw)
+            findings.extend(c for _b, _e, c in spans)
+            if not (self.strip_comments and comments):
+                return s
+            stripped = True
+            parts, pos = [], 0
+            for b, n in comments:
+                parts.append(raw[pos:b])
+                parts.append(b" ")
+                pos = b + n
+            parts.append(raw[pos:])
+            return b"".join(parts).decode("utf-8", "surrogatepass")
+
+        if self.fields is not None and isinstance(payload, dict):
+            new_payload = {k: (_walk_strings(v, fn) if k in self.fields else v) for k, v in payload.items()}
+        else:
+            new_payload = _walk_strings(payload, fn)
+        return (new_payload if stripped else payload), findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"dangerous sql detected: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        new_payload, findings = self.scan_payload(ctx.args)
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="sql")
+        meta = {"sql": sorted(set(findings))} if findings else {}   # audit: annotate only
+        if new_payload is not ctx.args:
+            return PluginResult.ok(new_payload, **meta)
+        return PluginResult.ok(**meta)
+
+    tool_pre_invoke = _apply
+    prompt_pre_fetch = _apply
+
+
 class SchemaGuardPlugin(Plugin):
     """Validate args/results against the tool's JSON schema (reference: schema_guard.py:168)."""
 
@@ -856,6 +977,7 @@ BUILTIN_PLUGINS = {
         PIIFilterPlugin,
         SecretsDetectionPlugin,
         EncodedExfilDetectionPlugin,
+        SqlSanitizerPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
