@@ -188,6 +188,8 @@ class GatewayEngine:
         await self.llm_proxy.aclose()
         await self.tool_service.aclose()
         await self.plugins.shutdown()
+        if self.gpu_pipeline is not None:
+            self.gpu_pipeline.close()
         self.observability.flush()
         self.metrics.flush()
         self.db.close()

@@ -226,6 +226,15 @@ class GpuPluginPipeline:
         if self.moderation is not None:
             self.classifier = GpuClassifier(self.moderation.model, device)
             self.feat_dim = self.moderation.dim
+        # native rescoring session (rescore.hip): the moderation rescan of a
+        # batch's rewritten rows as ONE call into session-owned buffers.
+        # Owned by the asyncio thread; FORGE_RESCORE_NATIVE=0 (read per
+        # batch) or any submit error takes the eager path instead
+        self._rescore: Optional[hip.RescoreSession] = None
+        if self.classifier is not None:
+            c = self.classifier
+            self._rescore = hip.RescoreSession(c.w1t, c.b1, c.w2t, c.b2)
+        self.rescore_native = self.rescore_eager = 0
 
         self.semcache: Optional[GpuSemanticCache] = None
         # the HBM cache only exists when the plugin has an EXPLICIT per-tool
@@ -706,6 +715,41 @@ class GpuPluginPipeline:
                 return
         await asyncio.to_thread(ev.synchronize)
 
+    def _rescore_submit(self, texts: List[bytes]) -> int:
+        """Submit the rescan of `texts` to the native session → its slot, or
+        -1 when the eager path has to run: no session, FORGE_RESCORE_NATIVE=0,
+        or the submit refused (too many rows or bytes, every slot busy)."""
+        sess = self._rescore
+        if sess is None or os.environ.get("FORGE_RESCORE_NATIVE", "1") == "0":
+            return -1
+        blob, offs = self._pb.concat_with_offsets(texts)
+        slot = sess.submit(blob, offs, len(texts))
+        return slot if slot >= 0 else -1
+
+    async def _rescore_collect(self, slot: int, n: int) -> np.ndarray:
+        """Await the slot's scores (one poll, then yielding polls with
+        _await_gpu's bound, then an off-loop wait), copy them out and release
+        the slot whatever happens."""
+        sess = self._rescore
+        try:
+            if not sess.poll(slot):
+                for _ in range(200000):
+                    await asyncio.sleep(0)
+                    if sess.poll(slot):
+                        break
+                else:
+                    await asyncio.to_thread(sess.wait, slot)
+            return sess.scores(slot, n)
+        finally:
+            sess.release(slot)
+
+    def close(self) -> None:
+        """Free the native rescoring session (engine shutdown). Batches after
+        this take the eager rescan."""
+        sess, self._rescore = self._rescore, None
+        if sess is not None:
+            sess.close()
+
     def _upload(self, arr: np.ndarray) -> torch.Tensor:
         """Stage a host array through the pinned arena → async H2D. Safe to
         call repeatedly within one pass; reset after the pass's sync."""
@@ -971,11 +1015,19 @@ class GpuPluginPipeline:
         # have it precomputed; python-lane entries serialize here
         texts2 = [scan_bytes[j] if j in scan_bytes else _sorted_json(a).encode()
                   for (j, a) in ok_items]
+        # scores2_t: None, the eager path's device tensor, or the native
+        # session's slot (an int)
         scores2_t = None
         if self.classifier is not None:
-            data2, beg2, end2 = pack_texts(texts2, self.device)
-            f2, _ = hip.featurize(data2, beg2, end2, self.feat_dim, pad_to=128)
-            scores2_t = self.classifier.forward(f2)[: len(ok_items)]
+            slot = self._rescore_submit(texts2)
+            if slot >= 0:
+                scores2_t = slot
+                self.rescore_native += 1
+            else:
+                data2, beg2, end2 = pack_texts(texts2, self.device)
+                f2, _ = hip.featurize(data2, beg2, end2, self.feat_dim, pad_to=128)
+                scores2_t = self.classifier.forward(f2)[: len(ok_items)]
+                self.rescore_eager += 1
 
         self._toc("rw_launch", t_sub)
         # the rescan kernels are IN FLIGHT — the sync happens inside the
@@ -1124,11 +1176,16 @@ class GpuPluginPipeline:
         rewritten texts (harm scan + moderation classifier) and emit the
         surviving (row, args) dispatch items."""
         t_sub = self._tic()
-        if scores2_t is not None:
-            await self._await_gpu()
-        self._toc("rw_sync", t_sub)
-        t_sub = self._tic()
-        scores2 = scores2_t.cpu().numpy() if scores2_t is not None else None
+        if isinstance(scores2_t, int):
+            scores2 = await self._rescore_collect(scores2_t, len(ok_items))
+            self._toc("rw_sync", t_sub)
+            t_sub = self._tic()
+        else:
+            if scores2_t is not None:
+                await self._await_gpu()
+            self._toc("rw_sync", t_sub)
+            t_sub = self._tic()
+            scores2 = scores2_t.cpu().numpy() if scores2_t is not None else None
 
         # hoisted gating: vectorized score reduction, per-tool applies from
         # the snapshot's arrays, id bytes only for rows that need a splice
@@ -1597,6 +1654,7 @@ class GpuPluginPipeline:
             "sql_routed": self.sql_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
+            "rescore_native": self.rescore_native, "rescore_eager": self.rescore_eager,
             "banks": {k: {"states": v.n_states, "classes": v.n_classes} for k, v in self.banks.items()},
         }
         if self.semcache is not None:

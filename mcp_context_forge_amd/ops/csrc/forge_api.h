@@ -22,6 +22,8 @@
 #define FORGE_ERR_ROW_ALIGN 9004  /* row length must be a multiple of 8 bf16 */
 #define FORGE_ERR_DECODE_SCAN 9005  /* decode_scan: bits, kw_max_len or keyword table size */
 #define FORGE_ERR_SQL_SCAN 9006   /* sql_scan: n_kw, kw_max_len or keyword table size */
+#define FORGE_ERR_RESCORE_ARGS 9007  /* rescore: row count, byte count, offsets or slot */
+#define FORGE_ERR_RESCORE_BUSY 9008  /* rescore_submit: every slot is in use */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -113,6 +115,11 @@ int forge_gemm_bt(const void* A, const void* BT, const void* bias, void* C,
 int forge_gemm_bt_v2(const void* A, const void* BT, const void* bias, void* C,
                      int M, int N, int K, int act, int out_bf16, void* stream);
 
+/* 64x64 tiles for M <= ~1k (gemm_skinny.hip): M%64, N%64, K%64, else
+ * FORGE_ERR_SHAPE with nothing launched. Bit-identical to the two above. */
+int forge_gemm_bt_skinny(const void* A, const void* BT, const void* bias, void* C,
+                         int M, int N, int K, int act, int out_bf16, void* stream);
+
 int forge_gemv_head(const void* A, const void* WT, const void* bias, void* out,
                     int M, int C, int K, int act, void* stream);
 
@@ -124,6 +131,39 @@ int forge_rows_gather_scatter_bf16(const void* src, const void* src_rows, const 
 
 int forge_verify_dot(const void* feats, const void* keys, const void* idx, void* out,
                      int M, int D, void* stream);
+
+/* ---- native rescoring session (rescore.hip) ----
+ * featurize + classifier + head over up to max_rows texts per submit, with
+ * every buffer owned by the session: a submit allocates nothing and never
+ * synchronises. w1t [hidden, dim] bf16, b1 f32[hidden], w2t [classes, hidden]
+ * bf16 and b2 f32[classes] are device pointers the caller keeps alive.
+ * max_rows, max_bytes (text bytes per submit) and n_slots <= 0 pick the
+ * defaults 1024, 512 * max_rows and 4. One thread owns a session; only
+ * forge_rescore_wait may run on another. Returns NULL on bad arguments or a
+ * failed allocation. */
+void* forge_rescore_new(const void* w1t, const void* b1, const void* w2t, const void* b2,
+                        int dim, int hidden, int classes,
+                        int max_rows, int64_t max_bytes, int n_slots);
+
+/* blob / offs are HOST memory: offs int64[n + 1] (concat_with_offsets
+ * layout), row i is blob[offs[i], offs[i + 1]). Returns the slot (>= 0) or a
+ * negative FORGE_ERR_RESCORE_* / hipError_t; argument and busy errors return
+ * before anything is launched. */
+int forge_rescore_submit(void* ctx, const uint8_t* blob, const int64_t* offs, int n, void* stream);
+
+/* 1 when the slot's scores are on the host, 0 while pending, negative on error. */
+int forge_rescore_poll(void* ctx, int slot);
+
+/* Blocks until the slot's scores are on the host: 1, or negative on error. */
+int forge_rescore_wait(void* ctx, int slot);
+
+/* Pinned host f32[max_rows][classes] of the slot; rows 0..n-1 are valid once
+ * poll / wait returned 1 and until the slot is released. */
+const float* forge_rescore_scores(void* ctx, int slot);
+
+void forge_rescore_release(void* ctx, int slot);
+
+void forge_rescore_free(void* ctx);
 
 /* ---- host data plane (pointers are host memory) ---- */
 

@@ -45,10 +45,18 @@ _API = {
     "forge_json_guard": _sig("i", "ppp i ii pp p"),
     "forge_gemm_bt": _sig("i", "pppp iii ii p"),
     "forge_gemm_bt_v2": _sig("i", "pppp iii ii p"),
+    "forge_gemm_bt_skinny": _sig("i", "pppp iii ii p"),
     "forge_gemv_head": _sig("i", "pppp iii i p"),
     "forge_rows_argmax_merge": _sig("i", "p iii p pp p"),
     "forge_rows_gather_scatter_bf16": _sig("i", "ppp p p ii p"),
     "forge_verify_dot": _sig("i", "ppp p ii p"),
+    "forge_rescore_new": _sig("p", "pppp iii i l i"),
+    "forge_rescore_submit": _sig("i", "p ss i p"),
+    "forge_rescore_poll": _sig("i", "p i"),
+    "forge_rescore_wait": _sig("i", "p i"),
+    "forge_rescore_scores": _sig("p", "p i"),
+    "forge_rescore_release": _sig("v", "p i"),
+    "forge_rescore_free": _sig("v", "p"),
     "forge_parallel_for": _sig("v", "i p p"),
     "forge_parse_envelopes": _sig("i", "pp i p pp pp pp"),
     "forge_upstream_call_batch": _sig("l", "ppp p i s p l pp"),
@@ -187,8 +195,9 @@ def scan_multi(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor,
     batch = beg.numel()
     if out is None:
         out = torch.zeros((bankset.n, batch), dtype=torch.int32, device=data.device)
-    else:
+    elif bankset.n == 0:
         out.zero_()
+    # with banks, the kernel writes every [bank, r < batch] element: no fill
     if bankset.n == 0 or batch == 0:
         return out
     _check("forge_scan_multi", _load().forge_scan_multi(
@@ -374,6 +383,40 @@ def gemm_bt(a: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = No
     return out
 
 
+# Same value as FORGE_ERR_SHAPE in csrc/forge_api.h.
+ERR_SHAPE = 9001
+
+# gemm_bt_skinny's tile (gemm_skinny.hip): M, N and K must be multiples of it.
+SKINNY_TILE = 64
+
+
+def gemm_skinny_enabled() -> bool:
+    return os.environ.get("FORGE_GEMM_SKINNY", "1") != "0"
+
+
+def gemm_skinny_fits(m: int, n: int, k: int) -> bool:
+    return m > 0 and n > 0 and k > 0 and m % SKINNY_TILE == 0 and n % SKINNY_TILE == 0 \
+        and k % SKINNY_TILE == 0
+
+
+def gemm_bt_skinny(a: torch.Tensor, bt: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   act: int = ACT_NONE, out_bf16: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_bt on 64x64 tiles (gemm_skinny.hip), for M up to about 1k: many
+    small workgroups where the big tiles leave most CUs idle. M%64==0,
+    N%64==0, K%64==0; bit-identical to gemm_bt."""
+    assert a.dtype == torch.bfloat16 and bt.dtype == torch.bfloat16
+    assert a.is_contiguous() and bt.is_contiguous()
+    m, k = a.shape
+    n, k2 = bt.shape
+    assert k == k2, (a.shape, bt.shape)
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=a.device)
+    _check("forge_gemm_bt_skinny", _load().forge_gemm_bt_skinny(
+        _ptr(a), _ptr(bt), _ptr(bias), _ptr(out), m, n, k, act, 1 if out_bf16 else 0, _stream()))
+    return out
+
+
 def gemv_head(a: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor] = None,
               act: int = ACT_NONE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     m, k = a.shape
@@ -408,6 +451,82 @@ def verify_dot(feats: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor) -> to
     _check("forge_verify_dot", _load().forge_verify_dot(
         _ptr(feats), _ptr(keys), _ptr(idx), _ptr(out), m, d, _stream()))
     return out
+
+
+# Same values as FORGE_ERR_RESCORE_* in csrc/forge_api.h (submit returns them negated).
+ERR_RESCORE_ARGS, ERR_RESCORE_BUSY = 9007, 9008
+
+
+class RescoreSession:
+    """Native rescoring session (rescore.hip): featurize + classifier + head
+    over a few rewritten texts, submitted by one call into buffers the session
+    owns (no allocation, no synchronise). Holds the weight tensors so their
+    device memory outlives the borrowed pointers.
+
+    One thread (the asyncio thread) owns a session; it is NOT thread-safe.
+    Only wait() may run on a helper thread."""
+
+    def __init__(self, w1t: torch.Tensor, b1: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor,
+                 max_rows: int = 1024, max_bytes: int = 0, n_slots: int = 4):
+        assert w1t.dtype == torch.bfloat16 and w2t.dtype == torch.bfloat16
+        assert b1.dtype == torch.float32 and b2.dtype == torch.float32
+        assert all(t.is_contiguous() for t in (w1t, b1, w2t, b2))
+        self._weights = (w1t, b1, w2t, b2)
+        self.hidden, self.dim = w1t.shape
+        self.classes = w2t.shape[0]
+        self.max_rows = max_rows
+        self.max_bytes = max_bytes if max_bytes > 0 else 512 * max_rows
+        self.n_slots = n_slots
+        self._lib = _load()
+        with torch.cuda.device(w1t.device):
+            ctx = self._lib.forge_rescore_new(_ptr(w1t), _ptr(b1), _ptr(w2t), _ptr(b2),
+                                              self.dim, self.hidden, self.classes,
+                                              max_rows, self.max_bytes, n_slots)
+        if not ctx:
+            raise ForgeHipError("forge_rescore_new failed")
+        self._ctx = ctypes.c_void_p(ctx)
+        # one numpy view per slot over its pinned scores
+        self._scores = []
+        for slot in range(n_slots):
+            ptr = self._lib.forge_rescore_scores(self._ctx, slot)
+            buf = (ctypes.c_float * (max_rows * self.classes)).from_address(ptr)
+            self._scores.append(np.frombuffer(buf, dtype=np.float32).reshape(max_rows, self.classes))
+
+    def submit(self, blob: bytes, offs: bytes, n: int) -> int:
+        """blob: the joined texts, offs: int64[n + 1] as bytes (pybridge
+        concat_with_offsets layout). → slot >= 0, or -ERR_RESCORE_* / a
+        negative hipError_t with nothing launched for the former."""
+        return self._lib.forge_rescore_submit(self._ctx, blob, offs, n, _stream())
+
+    def poll(self, slot: int) -> bool:
+        rc = self._lib.forge_rescore_poll(self._ctx, slot)
+        if rc < 0:
+            raise ForgeHipError(f"forge_rescore_poll failed with code {-rc}")
+        return rc == 1
+
+    def wait(self, slot: int) -> None:
+        rc = self._lib.forge_rescore_wait(self._ctx, slot)
+        if rc < 0:
+            raise ForgeHipError(f"forge_rescore_wait failed with code {-rc}")
+
+    def scores(self, slot: int, n: int) -> np.ndarray:
+        """A copy of the slot's first n score rows (valid after poll / wait)."""
+        return self._scores[slot][:n].copy()
+
+    def release(self, slot: int) -> None:
+        self._lib.forge_rescore_release(self._ctx, slot)
+
+    def close(self) -> None:
+        if self._ctx is not None:
+            self._scores = []
+            self._lib.forge_rescore_free(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------
