@@ -73,7 +73,20 @@ chain):
     Rows with a delete / update without where the plugin blocks, a blocked
     word, a comment when strip_comments is on, and every span with a
     backslash or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_sql_plugin.py checks the containment on the CPU).
+    (tests/test_sql_plugin.py checks the containment on the CPU);
+  * url_reputation is an exact prefilter in the same way. A span with no
+    backslash and no non-ASCII byte holds every string value verbatim
+    between quotes. '"' is a terminator and no scheme character, so every
+    URL of a value stands in the raw span with the same "://", the same
+    scheme (the opening quote ends the look-behind where the value began),
+    the same authority end (the closing quote stands where the value
+    ended), hence the same host, the same bits and the same table lookups.
+    Each URL is judged on its own and the per-span counts are sums (the
+    mask an OR) over the values plus whatever keys add: keys can only add
+    URLs. All outputs are integers, computed by url.hip exactly as by
+    ops/url.py with the plugin's own report mask. Rows with a reported URL,
+    and every span with a backslash or a non-ASCII byte, run the exact CPU
+    plugin (tests/test_url_plugin.py checks the containment on the CPU).
 """
 
 from __future__ import annotations
@@ -170,7 +183,7 @@ class GpuPluginPipeline:
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
         self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
-        self.sql = h.sql
+        self.sql, self.url = h.sql, h.url
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -220,6 +233,11 @@ class GpuPluginPipeline:
         if self.sql is not None:
             self._sql_kw = hip.DeviceScanTables(self.sql.keyword_tables(), device)
             self._sql_kw_len = torch.tensor(self.sql.keyword_lengths(), dtype=torch.int32, device=device)
+
+        # url_reputation: its domain table (slots, pool, powers) and report mask (url.hip)
+        self._url_table: Optional[hip.DeviceUrlTable] = None
+        if self.url is not None:
+            self._url_table = hip.DeviceUrlTable(self.url.domain_table(), device)
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -319,6 +337,7 @@ class GpuPluginPipeline:
         self.secrets_routed = 0  # requests the secrets prefilter sent to the CPU chain
         self.exfil_routed = 0    # requests the encoded-exfil prefilter sent to the CPU chain
         self.sql_routed = 0      # requests the sql prefilter sent to the CPU chain
+        self.url_routed = 0      # requests the url prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         self.timing_enabled = bool(os.environ.get("FORGE_PIPELINE_TIMING"))
         self.timing: Dict[str, float] = {}
@@ -450,7 +469,8 @@ class GpuPluginPipeline:
 
         fw_state = self._forward_foreign(rs, raws, user, users)
         if len(rs) and (tools.hostbound is not None or tools.secrets is not None
-                        or tools.exfil is not None or tools.sql is not None):
+                        or tools.exfil is not None or tools.sql is not None
+                        or tools.url is not None):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -509,7 +529,8 @@ class GpuPluginPipeline:
         if tools.hostbound is not None:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
-        # secrets_detection / encoded_exfil_detection / sql_sanitizer pre-pass:
+        # secrets_detection / encoded_exfil_detection / sql_sanitizer /
+        # url_reputation pre-pass:
         # rows of tools one of them is active for, whose raw argument bytes MAY
         # hold a finding, leave with the host-bound rows and run the exact
         # CPU chain, plugins included
@@ -522,10 +543,10 @@ class GpuPluginPipeline:
             return rows if rows.any() else None
 
         sec_rows, exf_rows = plugin_rows(tools.secrets), plugin_rows(tools.exfil)
-        sql_rows = plugin_rows(tools.sql)
-        if sec_rows is not None or exf_rows is not None or sql_rows is not None:
-            sec_flagged, exf_flagged, sql_flagged = await self._raw_prepass(
-                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows)
+        sql_rows, url_rows = plugin_rows(tools.sql), plugin_rows(tools.url)
+        if sec_rows is not None or exf_rows is not None or sql_rows is not None or url_rows is not None:
+            sec_flagged, exf_flagged, sql_flagged, url_flagged = await self._raw_prepass(
+                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows, url_rows)
             if sec_flagged is not None:
                 self.secrets_routed += int(sec_flagged.sum())
                 hb_mask |= sec_flagged
@@ -535,6 +556,9 @@ class GpuPluginPipeline:
             if sql_flagged is not None:
                 self.sql_routed += int(sql_flagged.sum())
                 hb_mask |= sql_flagged
+            if url_flagged is not None:
+                self.url_routed += int(url_flagged.sum())
+                hb_mask |= url_flagged
         if hb_mask.any():
             self.host_bound += n_bound
             await self._host_chain_rows(rs.rows[hb_mask], raws, row_user, server_id, rs.responses)
@@ -892,35 +916,45 @@ class GpuPluginPipeline:
         res |= (flags.cpu().numpy() & 1) != 0
         return res
 
+    def _url_flags(self, out, n: int) -> np.ndarray:
+        """URL prefilter over hip.url_scan outputs (launched with the plugin's
+        report mask): a row is flagged when it holds a reported URL, or when
+        its span holds a backslash or a non-ASCII byte. Integer outputs,
+        equal to the plugin's own: nothing to round."""
+        counts, _mask, _first, flags = out
+        return (counts.cpu().numpy()[:, 3] > 0) | ((flags.cpu().numpy() & 1) != 0)
+
     async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
                            sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray],
-                           sql_rows: Optional[np.ndarray] = None
-                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
-        """secrets_detection, encoded_exfil_detection and sql_sanitizer
-        prefilters over raw argument bytes → (bool[m] or None) per plugin,
-        True where the row must run the exact CPU chain; `sec_rows` /
-        `exf_rows` / `sql_rows` mark the rows of tools each plugin is active
-        for (None: not this batch). Eager, under _gpu_lock, ONE upload for
-        all: the secrets format bank (scan.hip) and one token_entropy launch
-        per alphabet, one decode_scan launch per encoding, one sql_scan
-        launch in boundary mode, over the union of the marked rows; every
-        other row gets an empty span, and each verdict is masked with its
-        own plugin's rows. The blob is uploaded here and again by pass 1 on
+                           sql_rows: Optional[np.ndarray] = None, url_rows: Optional[np.ndarray] = None
+                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray],
+                                      Optional[np.ndarray]]:
+        """secrets_detection, encoded_exfil_detection, sql_sanitizer and
+        url_reputation prefilters over raw argument bytes → (bool[m] or None)
+        per plugin, True where the row must run the exact CPU chain;
+        `sec_rows` / `exf_rows` / `sql_rows` / `url_rows` mark the rows of
+        tools each plugin is active for (None: not this batch). Eager, under
+        _gpu_lock, ONE upload for all: the secrets format bank (scan.hip) and
+        one token_entropy launch per alphabet, one decode_scan launch per
+        encoding, one sql_scan launch in boundary mode, one url_scan launch,
+        over the union of the marked rows; every other row gets an empty
+        span, and each verdict is masked with its own plugin's rows. The blob is uploaded here and again by pass 1 on
         purpose — folding this pre-pass into the captured pass-1 graph is a
         later change. Timed as gp0_secrets when secrets_detection takes
-        part, else as gp0_exfil when encoded_exfil_detection does, as
-        gp0_sql when sql_sanitizer alone does."""
+        part, else as gp0_exfil when encoded_exfil_detection does, else
+        as gp0_sql when sql_sanitizer does, as gp0_url when url_reputation
+        alone does."""
         t0 = self._tic()
         m = args_b.shape[0]
         rows = np.zeros(m, dtype=bool)
-        for part in (sec_rows, exf_rows, sql_rows):
+        for part in (sec_rows, exf_rows, sql_rows, url_rows):
             if part is not None:
                 rows |= part
         sb = np.ascontiguousarray(np.where(rows, args_b, 0).astype(np.int32))
         se = np.ascontiguousarray(np.where(rows, args_e, 0).astype(np.int32))
 
         def launch(data_t, beg_t, end_t):
-            mask_t = ent = dec = sq = None
+            mask_t = ent = dec = sq = ur = None
             if sec_rows is not None:
                 if "secrets" in self.banks:
                     mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0]
@@ -929,10 +963,12 @@ class GpuPluginPipeline:
                 dec = self._exfil_launch(data_t, beg_t, end_t)
             if sql_rows is not None:
                 sq = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
-            return mask_t, ent, dec, sq
+            if url_rows is not None:
+                ur = hip.url_scan(data_t, beg_t, end_t, self._url_table, self.url.report_mask())
+            return mask_t, ent, dec, sq, ur
 
-        _mm, _scores, (mask_t, ent, dec, sq) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        sec_flagged = exf_flagged = sql_flagged = None
+        _mm, _scores, (mask_t, ent, dec, sq, ur) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
+        sec_flagged = exf_flagged = sql_flagged = url_flagged = None
         if sec_rows is not None:
             sec_flagged = self._entropy_flags(ent, m)
             if mask_t is not None:
@@ -942,8 +978,11 @@ class GpuPluginPipeline:
             exf_flagged = self._exfil_flags(dec, m) & exf_rows
         if sql_rows is not None:
             sql_flagged = self._sql_flags(sq, m) & sql_rows
-        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil" if exf_rows is not None else "gp0_sql", t0)
-        return sec_flagged, exf_flagged, sql_flagged
+        if url_rows is not None:
+            url_flagged = self._url_flags(ur, m) & url_rows
+        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil" if exf_rows is not None
+                  else "gp0_sql" if sql_rows is not None else "gp0_url", t0)
+        return sec_flagged, exf_flagged, sql_flagged, url_flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1651,7 +1690,7 @@ class GpuPluginPipeline:
             "slow_path": self.slow_path, "blocked": self.blocked, "cache_hits": self.cache_hits,
             "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
             "exfil_routed": self.exfil_routed,
-            "sql_routed": self.sql_routed,
+            "sql_routed": self.sql_routed, "url_routed": self.url_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "rescore_native": self.rescore_native, "rescore_eager": self.rescore_eager,

@@ -24,6 +24,7 @@
 #define FORGE_ERR_SQL_SCAN 9006   /* sql_scan: n_kw, kw_max_len or keyword table size */
 #define FORGE_ERR_RESCORE_ARGS 9007  /* rescore: row count, byte count, offsets or slot */
 #define FORGE_ERR_RESCORE_BUSY 9008  /* rescore_submit: every slot is in use */
+#define FORGE_ERR_URL_SCAN 9009   /* url_scan: slot count, pool size or report_mask */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -48,6 +49,21 @@
 #define FORGE_SQL_SCAN_MIN_KW 6
 #define FORGE_SQL_SCAN_MAX_KW 29
 #define FORGE_SQL_SCAN_KW_MAX_LEN 16
+
+/* forge_url_scan probes a domain table of up to FORGE_URL_SCAN_LDS_SLOTS
+ * slots in LDS (staged once per block) and a larger one in global memory. A
+ * slot count that is no power of two or outside
+ * FORGE_URL_SCAN_MIN_SLOTS..FORGE_URL_SCAN_MAX_SLOTS, a pool over
+ * FORGE_URL_SCAN_POOL_MAX bytes or a report_mask with bits outside
+ * FORGE_URL_SCAN_ALL_BITS are an argument error. An authority is analysed up
+ * to FORGE_URL_SCAN_AUTH_MAX bytes. ops/hip.py carries the first as
+ * URL_SCAN_LDS_SLOTS; ops/url.py has them all. */
+#define FORGE_URL_SCAN_LDS_SLOTS 1024
+#define FORGE_URL_SCAN_MIN_SLOTS 2
+#define FORGE_URL_SCAN_MAX_SLOTS (1 << 20)
+#define FORGE_URL_SCAN_POOL_MAX ((int64_t)1 << 31)
+#define FORGE_URL_SCAN_ALL_BITS 1023
+#define FORGE_URL_SCAN_AUTH_MAX 256
 
 typedef void (*forge_task_fn)(int index, void* ctx);
 
@@ -100,6 +116,22 @@ int forge_sql_scan(const void* data, const void* beg, const void* end_, int batc
                    int n_states, int n_classes, const void* kw_len, int n_kw, int kw_max_len,
                    int dquote_boundary,
                    void* out_counts, void* out_blocked, void* out_first, void* out_flags,
+                   void* stream);
+
+/* One wave per request: every "://" with a scheme before it is a URL; delimit
+ * its authority and host (userinfo, port, trailing dots), classify it (bits
+ * 0..9: blocked, http, other scheme, numeric, bracket, userinfo, punycode,
+ * non-ascii, overlong, empty host) and look every label-start suffix of the
+ * host up in the domain table: slots u32[n_slots][4] (key, tag 1 blocked / 2
+ * allowed / 0 empty, pool offset, length), pool the domain bytes, powers
+ * u32[2][256]; an allowed suffix beats a blocked one. out_counts
+ * i32[batch][4] (urls, allowed, blocked-domain, reported: bits & report_mask),
+ * out_mask i32[batch], out_first i32[batch][2] (absolute begin, length of the
+ * first reported URL or -1, 0), out_flags i32[batch]. */
+int forge_url_scan(const void* data, const void* beg, const void* end_, int batch,
+                   const void* slots, int n_slots, const void* pool, int64_t pool_bytes,
+                   const void* powers, int report_mask,
+                   void* out_counts, void* out_mask, void* out_first, void* out_flags,
                    void* stream);
 
 int forge_featurize(const void* data, const void* beg, const void* end_, int batch, int dim,

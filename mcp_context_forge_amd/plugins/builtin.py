@@ -14,6 +14,10 @@ Per-plugin reference analogs (behavioral port, no code copied):
                        UPDATE without WHERE, outside strings and comments;
                        block / audit, optional comment stripping). Opt-in: not
                        in the default chain
+  url_reputation     → cpex-url-reputation (blocked / allowed domains with
+                       subdomain matching, plain http, raw-IP, userinfo and
+                       punycode hosts; block / audit). Opt-in: not in the
+                       default chain
   schema_guard      → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
@@ -584,6 +588,102 @@ class SqlSanitizerPlugin(Plugin):
     prompt_pre_fetch = _apply
 
 
+class UrlReputationPlugin(Plugin):
+    """Stop links to blocked or suspicious hosts travelling in arguments:
+    every `scheme://` of every string value is a URL whose host is delimited
+    (userinfo, port, trailing dots) and looked up, suffix by suffix, in the
+    blocked and allowed domain lists (ops/url.py; url.hip on the GPU path).
+    `evil.test` covers `a.b.evil.test` and not `notevil.test`; an allowed
+    suffix beats a blocked one for that URL. Priority 9: after sql_sanitizer
+    and before deny_filter and every rewriter, which is what makes the
+    pipeline's raw-byte prefilter sound. Pre hooks only.
+
+    Config: action block (default, code "url") | audit, blocked_domains,
+    whitelist_domains (each 1 to 253 bytes of [a-z0-9._-] in any case, at most
+    2^19 in total, none listed twice), block_non_secure_http (true: http and
+    every scheme other than https is a finding), use_heuristic_check (true:
+    numeric, bracketed, userinfo, punycode and non-ASCII hosts and authorities
+    over 256 bytes are findings), min_findings_to_block (1).
+
+    A resource URI names its own scheme (`res://`, `file://`, ...), which the
+    resource layer dispatches on: on resource_pre_fetch a scheme other than
+    http or https is no finding; plain http, the host checks and the domain
+    lists apply as everywhere.
+    """
+
+    name = "url_reputation"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.PROMPT_PRE_FETCH, HookType.RESOURCE_PRE_FETCH)
+    priority = 9
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import url as _url
+
+        self._url = _url
+        self.action: str = self.config.get("action", "block")  # block | audit
+        if self.action not in ("block", "audit"):
+            raise ValueError(f"unknown url_reputation action {self.action!r}")
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self.block_non_secure_http = bool(self.config.get("block_non_secure_http", True))
+        self.use_heuristic_check = bool(self.config.get("use_heuristic_check", True))
+        self.blocked_domains: List[str] = [str(d) for d in self.config.get("blocked_domains") or []]
+        self.whitelist_domains: List[str] = [str(d) for d in self.config.get("whitelist_domains") or []]
+        self._table = _url.compile_domains(self.blocked_domains, self.whitelist_domains)   # raises on a bad list
+
+    def domain_table(self):
+        """The compiled url.DomainTable (what hip.DeviceUrlTable uploads)."""
+        return self._table
+
+    def report_mask(self) -> int:
+        """The category bits that are findings under this configuration."""
+        u = self._url
+        return (u.BLOCKED | (u.SCHEME_BITS if self.block_non_secure_http else 0)
+                | (u.HEURISTIC_BITS if self.use_heuristic_check else 0))
+
+    def find_spans(self, raw: bytes, mask: Optional[int] = None) -> List[Tuple[int, int, str]]:
+        """Every finding in one string's UTF-8 bytes as (beg, end, category):
+        one per reported category (of `mask`, default report_mask()) of every
+        URL that is not allowed."""
+        want = self.report_mask() if mask is None else mask
+        urls = self._url.url_scan_reference(raw, self._table.domains, want)[0]
+        return [(b, b + n, c) for (b, n, bits, allowed) in urls if not allowed
+                for c in self._url.category_names(bits & want)]
+
+    def scan_payload(self, payload: Any, mask: Optional[int] = None) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value. → (payload, findings): the
+        payload as it came, one category name per finding."""
+        findings: List[str] = []
+
+        def fn(s: str) -> str:
+            findings.extend(c for _b, _e, c in self.find_spans(s.encode("utf-8", "surrogatepass"), mask))
+            return s
+
+        _walk_strings(payload, fn)
+        return payload, findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"url reputation: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        mask = self.report_mask()
+        if ctx.hook == HookType.RESOURCE_PRE_FETCH:
+            mask &= ~self._url.OTHER_SCHEME
+        _payload, findings = self.scan_payload(ctx.args, mask)
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="url")
+        meta = {"url": sorted(set(findings))} if findings else {}   # audit: annotate only
+        return PluginResult.ok(**meta)
+
+    tool_pre_invoke = _apply
+    prompt_pre_fetch = _apply
+    resource_pre_fetch = _apply
+
+
 class SchemaGuardPlugin(Plugin):
     """Validate args/results against the tool's JSON schema (reference: schema_guard.py:168)."""
 
@@ -978,6 +1078,7 @@ BUILTIN_PLUGINS = {
         SecretsDetectionPlugin,
         EncodedExfilDetectionPlugin,
         SqlSanitizerPlugin,
+        UrlReputationPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
