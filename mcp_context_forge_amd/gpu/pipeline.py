@@ -86,7 +86,23 @@ chain):
     URLs. All outputs are integers, computed by url.hip exactly as by
     ops/url.py with the plugin's own report mask. Rows with a reported URL,
     and every span with a backslash or a non-ASCII byte, run the exact CPU
-    plugin (tests/test_url_plugin.py checks the containment on the CPU).
+    plugin (tests/test_url_plugin.py checks the containment on the CPU);
+  * account_number_detection is an exact prefilter in the same way. In a
+    span with no backslash and no non-ASCII byte every string value stands
+    verbatim between quotes. '"' is not a digit, a separator, a letter, '_'
+    or '.', so it judges every boundary exactly as a string edge does: a
+    card run of a value is the same run in the raw span, with the same
+    digits, the same verdicts on the bytes before and after it and the
+    same Luhn sum, and an IBAN start of a value is one in the raw span,
+    whose walk stops where the value ends. Findings do not consume one
+    another and the per-span counts are sums over the values plus whatever
+    keys and bare numbers add: those can only add candidates. So the
+    prefilter may over-flag and never under-flags. All outputs are
+    integers, computed by account.hip exactly as by ops/account.py with the
+    plugin's own country table. Rows with a valid card or IBAN of a
+    configured kind, and every span with a backslash or a non-ASCII byte,
+    run the exact CPU plugin (tests/test_account_plugin.py checks the
+    containment on the CPU).
 """
 
 from __future__ import annotations
@@ -183,7 +199,7 @@ class GpuPluginPipeline:
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
         self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
-        self.sql, self.url = h.sql, h.url
+        self.sql, self.url, self.account = h.sql, h.url, h.account
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -238,6 +254,11 @@ class GpuPluginPipeline:
         self._url_table: Optional[hip.DeviceUrlTable] = None
         if self.url is not None:
             self._url_table = hip.DeviceUrlTable(self.url.domain_table(), device)
+
+        # account_number_detection: its country length table (account.hip)
+        self._iban_table: Optional[hip.DeviceIbanTable] = None
+        if self.account is not None:
+            self._iban_table = hip.DeviceIbanTable(self.account.iban_table(), device)
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -338,6 +359,7 @@ class GpuPluginPipeline:
         self.exfil_routed = 0    # requests the encoded-exfil prefilter sent to the CPU chain
         self.sql_routed = 0      # requests the sql prefilter sent to the CPU chain
         self.url_routed = 0      # requests the url prefilter sent to the CPU chain
+        self.account_routed = 0  # requests the account-number prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         self.timing_enabled = bool(os.environ.get("FORGE_PIPELINE_TIMING"))
         self.timing: Dict[str, float] = {}
@@ -470,7 +492,7 @@ class GpuPluginPipeline:
         fw_state = self._forward_foreign(rs, raws, user, users)
         if len(rs) and (tools.hostbound is not None or tools.secrets is not None
                         or tools.exfil is not None or tools.sql is not None
-                        or tools.url is not None):
+                        or tools.url is not None or tools.account is not None):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -530,7 +552,7 @@ class GpuPluginPipeline:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
         # secrets_detection / encoded_exfil_detection / sql_sanitizer /
-        # url_reputation pre-pass:
+        # url_reputation / account_number_detection pre-pass:
         # rows of tools one of them is active for, whose raw argument bytes MAY
         # hold a finding, leave with the host-bound rows and run the exact
         # CPU chain, plugins included
@@ -544,9 +566,11 @@ class GpuPluginPipeline:
 
         sec_rows, exf_rows = plugin_rows(tools.secrets), plugin_rows(tools.exfil)
         sql_rows, url_rows = plugin_rows(tools.sql), plugin_rows(tools.url)
-        if sec_rows is not None or exf_rows is not None or sql_rows is not None or url_rows is not None:
-            sec_flagged, exf_flagged, sql_flagged, url_flagged = await self._raw_prepass(
-                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows, url_rows)
+        acct_rows = plugin_rows(tools.account)
+        if (sec_rows is not None or exf_rows is not None or sql_rows is not None or url_rows is not None
+                or acct_rows is not None):
+            sec_flagged, exf_flagged, sql_flagged, url_flagged, acct_flagged = await self._raw_prepass(
+                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows, url_rows, acct_rows=acct_rows)
             if sec_flagged is not None:
                 self.secrets_routed += int(sec_flagged.sum())
                 hb_mask |= sec_flagged
@@ -559,6 +583,9 @@ class GpuPluginPipeline:
             if url_flagged is not None:
                 self.url_routed += int(url_flagged.sum())
                 hb_mask |= url_flagged
+            if acct_flagged is not None:
+                self.account_routed += int(acct_flagged.sum())
+                hb_mask |= acct_flagged
         if hb_mask.any():
             self.host_bound += n_bound
             await self._host_chain_rows(rs.rows[hb_mask], raws, row_user, server_id, rs.responses)
@@ -924,37 +951,51 @@ class GpuPluginPipeline:
         counts, _mask, _first, flags = out
         return (counts.cpu().numpy()[:, 3] > 0) | ((flags.cpu().numpy() & 1) != 0)
 
+    def _account_flags(self, out, n: int) -> np.ndarray:
+        """Account-number prefilter over hip.account_scan outputs: a row is
+        flagged when it holds a valid card or IBAN of a kind the plugin
+        reports, or when its span holds a backslash or a non-ASCII byte.
+        Integer outputs, equal to the plugin's own: nothing to round."""
+        counts, _kinds, _first, flags = out
+        c = counts.cpu().numpy()
+        valid = (c[:, 1] if self.account.detect_cards else 0) + (c[:, 3] if self.account.detect_ibans else 0)
+        return (valid > 0) | ((flags.cpu().numpy() & 1) != 0)
+
     async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
                            sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray],
-                           sql_rows: Optional[np.ndarray] = None, url_rows: Optional[np.ndarray] = None
+                           sql_rows: Optional[np.ndarray] = None, url_rows: Optional[np.ndarray] = None,
+                           *, acct_rows: Optional[np.ndarray] = None
                            ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray],
-                                      Optional[np.ndarray]]:
-        """secrets_detection, encoded_exfil_detection, sql_sanitizer and
-        url_reputation prefilters over raw argument bytes → (bool[m] or None)
-        per plugin, True where the row must run the exact CPU chain;
-        `sec_rows` / `exf_rows` / `sql_rows` / `url_rows` mark the rows of
-        tools each plugin is active for (None: not this batch). Eager, under
-        _gpu_lock, ONE upload for all: the secrets format bank (scan.hip) and
-        one token_entropy launch per alphabet, one decode_scan launch per
-        encoding, one sql_scan launch in boundary mode, one url_scan launch,
-        over the union of the marked rows; every other row gets an empty
-        span, and each verdict is masked with its own plugin's rows. The blob is uploaded here and again by pass 1 on
+                                      Optional[np.ndarray], Optional[np.ndarray]]:
+        """secrets_detection, encoded_exfil_detection, sql_sanitizer,
+        url_reputation and account_number_detection prefilters over raw
+        argument bytes → (bool[m] or None) per plugin, True where the row
+        must run the exact CPU chain; `sec_rows` / `exf_rows` / `sql_rows` /
+        `url_rows` / `acct_rows` mark the rows of tools each plugin is active
+        for (None: not this batch). Eager, under _gpu_lock, ONE upload for
+        all: the secrets format bank (scan.hip) and one token_entropy launch
+        per alphabet, one decode_scan launch per encoding, one sql_scan
+        launch in boundary mode, one url_scan launch, one account_scan
+        launch, over the union of the marked rows; every other row gets an
+        empty span, and each verdict is masked with its own plugin's rows.
+        The blob is uploaded here and again by pass 1 on
         purpose — folding this pre-pass into the captured pass-1 graph is a
         later change. Timed as gp0_secrets when secrets_detection takes
         part, else as gp0_exfil when encoded_exfil_detection does, else
-        as gp0_sql when sql_sanitizer does, as gp0_url when url_reputation
+        as gp0_sql when sql_sanitizer does, else as gp0_url when
+        url_reputation does, as gp0_account when account_number_detection
         alone does."""
         t0 = self._tic()
         m = args_b.shape[0]
         rows = np.zeros(m, dtype=bool)
-        for part in (sec_rows, exf_rows, sql_rows, url_rows):
+        for part in (sec_rows, exf_rows, sql_rows, url_rows, acct_rows):
             if part is not None:
                 rows |= part
         sb = np.ascontiguousarray(np.where(rows, args_b, 0).astype(np.int32))
         se = np.ascontiguousarray(np.where(rows, args_e, 0).astype(np.int32))
 
         def launch(data_t, beg_t, end_t):
-            mask_t = ent = dec = sq = ur = None
+            mask_t = ent = dec = sq = ur = ac = None
             if sec_rows is not None:
                 if "secrets" in self.banks:
                     mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0]
@@ -965,10 +1006,12 @@ class GpuPluginPipeline:
                 sq = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
             if url_rows is not None:
                 ur = hip.url_scan(data_t, beg_t, end_t, self._url_table, self.url.report_mask())
-            return mask_t, ent, dec, sq, ur
+            if acct_rows is not None:
+                ac = hip.account_scan(data_t, beg_t, end_t, self._iban_table, self.account.report_mask())
+            return mask_t, ent, dec, sq, ur, ac
 
-        _mm, _scores, (mask_t, ent, dec, sq, ur) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        sec_flagged = exf_flagged = sql_flagged = url_flagged = None
+        _mm, _scores, (mask_t, ent, dec, sq, ur, ac) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
+        sec_flagged = exf_flagged = sql_flagged = url_flagged = acct_flagged = None
         if sec_rows is not None:
             sec_flagged = self._entropy_flags(ent, m)
             if mask_t is not None:
@@ -980,9 +1023,12 @@ class GpuPluginPipeline:
             sql_flagged = self._sql_flags(sq, m) & sql_rows
         if url_rows is not None:
             url_flagged = self._url_flags(ur, m) & url_rows
+        if acct_rows is not None:
+            acct_flagged = self._account_flags(ac, m) & acct_rows
         self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil" if exf_rows is not None
-                  else "gp0_sql" if sql_rows is not None else "gp0_url", t0)
-        return sec_flagged, exf_flagged, sql_flagged, url_flagged
+                  else "gp0_sql" if sql_rows is not None else "gp0_url" if url_rows is not None
+                  else "gp0_account", t0)
+        return sec_flagged, exf_flagged, sql_flagged, url_flagged, acct_flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1691,6 +1737,7 @@ class GpuPluginPipeline:
             "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
             "exfil_routed": self.exfil_routed,
             "sql_routed": self.sql_routed, "url_routed": self.url_routed,
+            "account_routed": self.account_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "rescore_native": self.rescore_native, "rescore_eager": self.rescore_eager,

@@ -25,6 +25,7 @@
 #define FORGE_ERR_RESCORE_ARGS 9007  /* rescore: row count, byte count, offsets or slot */
 #define FORGE_ERR_RESCORE_BUSY 9008  /* rescore_submit: every slot is in use */
 #define FORGE_ERR_URL_SCAN 9009   /* url_scan: slot count, pool size or report_mask */
+#define FORGE_ERR_ACCOUNT_SCAN 9010   /* account_scan: report_mask */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -64,6 +65,16 @@
 #define FORGE_URL_SCAN_POOL_MAX ((int64_t)1 << 31)
 #define FORGE_URL_SCAN_ALL_BITS 1023
 #define FORGE_URL_SCAN_AUTH_MAX 256
+
+/* forge_account_scan reads a table of FORGE_ACCOUNT_SCAN_TABLE_BYTES country
+ * lengths, indexed 26 * (c0 - 'A') + (c1 - 'A'); an entry outside
+ * FORGE_ACCOUNT_SCAN_MIN_LEN..FORGE_ACCOUNT_SCAN_MAX_LEN is an unknown
+ * country. A report_mask with bits outside FORGE_ACCOUNT_SCAN_ALL_KINDS (1
+ * card, 2 IBAN) is an argument error. ops/account.py has them all. */
+#define FORGE_ACCOUNT_SCAN_TABLE_BYTES 676
+#define FORGE_ACCOUNT_SCAN_MIN_LEN 15
+#define FORGE_ACCOUNT_SCAN_MAX_LEN 34
+#define FORGE_ACCOUNT_SCAN_ALL_KINDS 3
 
 typedef void (*forge_task_fn)(int index, void* ctx);
 
@@ -133,6 +144,20 @@ int forge_url_scan(const void* data, const void* beg, const void* end_, int batc
                    const void* powers, int report_mask,
                    void* out_counts, void* out_mask, void* out_first, void* out_flags,
                    void* stream);
+
+/* One wave per request: payment cards (runs of 13..19 digits with single ' '
+ * or '-' separators, first digit not 0, no [A-Za-z_.] before and no [A-Za-z_]
+ * after, valid by Luhn) and IBANs (two letters, two digits, the length
+ * iban_len u8[676] gives for the country, single spaces allowed, valid when
+ * the rotated base-36 number is 1 mod 97). out_counts i32[batch][4] (card
+ * candidates, valid cards, IBAN candidates, valid IBANs), out_kinds i32[batch]
+ * (bit 0 a valid card, bit 1 a valid IBAN), out_first i32[batch][2] (absolute
+ * begin, length of the first valid finding of a kind in report_mask, or -1, 0),
+ * out_flags i32[batch]. */
+int forge_account_scan(const void* data, const void* beg, const void* end_, int batch,
+                       const void* iban_len, int report_mask,
+                       void* out_counts, void* out_kinds, void* out_first, void* out_flags,
+                       void* stream);
 
 int forge_featurize(const void* data, const void* beg, const void* end_, int batch, int dim,
                     void* out_bf16, void* out_f32, void* stream);

@@ -16,7 +16,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import entropy, exfil, sql, url
+from . import account, entropy, exfil, sql, url
 from .dfa import ScanTables
 
 
@@ -42,6 +42,7 @@ _API = {
     "forge_decode_scan": _sig("i", "ppp i piii ppp iii pppp p"),
     "forge_sql_scan": _sig("i", "ppp i ppp ii pii i pppp p"),
     "forge_url_scan": _sig("i", "ppp i pi pl p i pppp p"),
+    "forge_account_scan": _sig("i", "ppp i pi pppp p"),
     "forge_featurize": _sig("i", "ppp ii pp p"),
     "forge_json_guard": _sig("i", "ppp i ii pp p"),
     "forge_gemm_bt": _sig("i", "pppp iii ii p"),
@@ -366,6 +367,40 @@ def url_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table: De
         int(report_mask),
         _ptr(counts), _ptr(mask), _ptr(first), _ptr(flags), _stream()))
     return counts, mask, first, flags
+
+
+class DeviceIbanTable:
+    """The 676 country lengths of account.compile_iban_lengths in device memory."""
+
+    def __init__(self, table: bytes, device: str = "cuda"):
+        if len(table) != account.IBAN_TABLE_BYTES:
+            raise ValueError(f"an IBAN length table holds {account.IBAN_TABLE_BYTES} bytes, got {len(table)}")
+        self.meta = bytes(table)
+        self.lengths = torch.from_numpy(np.frombuffer(self.meta, dtype=np.uint8).copy()).to(device)
+
+
+def account_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table: DeviceIbanTable,
+                 report_mask: int, out: Optional[Tuple[torch.Tensor, ...]] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Find the payment cards (Luhn) and IBANs (country length, mod 97) of each
+    span, one wave per request (account.hip; oracle ops/account.py
+    account_scan_reference). report_mask: the kinds (account.CARD,
+    account.IBAN) whose valid findings `first` reports.
+    → (counts i32[B, 4], kinds i32[B], first i32[B, 2], flags i32[B]). The
+    kernel writes every element; `out` (those four, preallocated) makes the
+    call graph-capture safe."""
+    batch = beg.numel()
+    if out is None:
+        dev = data.device
+        out = (torch.empty((batch, 4), dtype=torch.int32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev),
+               torch.empty((batch, 2), dtype=torch.int32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev))
+    counts, kinds, first, flags = out
+    _check("forge_account_scan", _load().forge_account_scan(
+        _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(table.lengths), int(report_mask),
+        _ptr(counts), _ptr(kinds), _ptr(first), _ptr(flags), _stream()))
+    return counts, kinds, first, flags
 
 
 def featurize(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, dim: int,

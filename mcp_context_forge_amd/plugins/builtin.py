@@ -18,6 +18,11 @@ Per-plugin reference analogs (behavioral port, no code copied):
                        subdomain matching, plain http, raw-IP, userinfo and
                        punycode hosts; block / audit). Opt-in: not in the
                        default chain
+  account_number_detection → payment cards by Luhn (13 to 19 digits, single
+                       space or dash separators) and IBANs by country length
+                       and mod 97, which pii_filter's 4-4-4-4 pattern cannot
+                       tell from order numbers; block / redact / audit.
+                       Opt-in: not in the default chain
   schema_guard      → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
@@ -684,6 +689,107 @@ class UrlReputationPlugin(Plugin):
     resource_pre_fetch = _apply
 
 
+class AccountNumberDetectionPlugin(Plugin):
+    """Stop account numbers travelling in arguments: payment cards — runs of
+    13 to 19 digits, single spaces or dashes allowed between digits, that
+    pass the Luhn check — and IBANs of the known countries that have the
+    country's length and pass mod 97 (ops/account.py; account.hip on the GPU
+    path). Only upper-case IBANs count. Priority 9: with url_reputation,
+    before deny_filter and every rewriter, which is what makes the pipeline's
+    raw-byte prefilter sound. Pre hooks only.
+
+    Config: action block (default, code "account") | redact | audit,
+    detect_cards (true), detect_ibans (true), iban_lengths ({"XX": length}
+    merged over account.DEFAULT_IBAN_LENGTHS; 0 drops a country),
+    min_findings_to_block (1). Redact replaces a card with [CARD_REDACTED] and
+    an IBAN with [IBAN_REDACTED]; of two findings that overlap, the one that
+    begins first is replaced.
+    """
+
+    name = "account_number_detection"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.PROMPT_PRE_FETCH)
+    priority = 9
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import account as _account
+
+        self._account = _account
+        self.action: str = self.config.get("action", "block")  # block | redact | audit
+        if self.action not in ("block", "redact", "audit"):
+            raise ValueError(f"unknown account_number_detection action {self.action!r}")
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self.detect_cards = bool(self.config.get("detect_cards", True))
+        self.detect_ibans = bool(self.config.get("detect_ibans", True))
+        self._iban_table = _account.compile_iban_lengths(self.config.get("iban_lengths"))   # raises on a bad entry
+
+    def iban_table(self) -> bytes:
+        """The 676 country lengths (what hip.DeviceIbanTable uploads)."""
+        return self._iban_table
+
+    def report_mask(self) -> int:
+        """The kinds that are findings under this configuration."""
+        a = self._account
+        return (a.CARD if self.detect_cards else 0) | (a.IBAN if self.detect_ibans else 0)
+
+    def find_spans(self, raw: bytes) -> List[Tuple[int, int, str]]:
+        """Every finding in one string's UTF-8 bytes as (beg, end, kind name), by begin."""
+        want = self.report_mask()
+        found = self._account.account_scan_reference(raw, self._iban_table, want)[0]
+        return [(b, b + n, self._account.KIND_NAMES[kind]) for (b, n, kind) in found if kind & want]
+
+    @staticmethod
+    def _redact(raw: bytes, spans: List[Tuple[int, int, str]]) -> bytes:
+        kept: List[Tuple[int, int, str]] = []
+        for span in spans:   # by begin: of two that overlap the first stays
+            if not kept or span[0] >= kept[-1][1]:
+                kept.append(span)
+        for b, e, kind in reversed(kept):   # right to left, so the spans before stay valid
+            raw = raw[:b] + b"[" + kind.upper().encode() + b"_REDACTED]" + raw[e:]
+        return raw
+
+    def scan_payload(self, payload: Any) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value. → (payload, findings): the
+        payload has every finding replaced when action is "redact" (otherwise
+        it is returned as is); findings holds one kind name per finding."""
+        findings: List[str] = []
+        redact = self.action == "redact"
+
+        def fn(s: str) -> str:
+            raw = s.encode("utf-8", "surrogatepass")
+            spans = self.find_spans(raw)
+            if not spans:
+                return s
+            findings.extend(c for _b, _e, c in spans)
+            if not redact:
+                return s
+            return self._redact(raw, spans).decode("utf-8", "surrogatepass")
+
+        new_payload = _walk_strings(payload, fn)
+        return (new_payload if redact and findings else payload), findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"account numbers detected: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        new_payload, findings = self.scan_payload(ctx.args)
+        if not findings:
+            return PluginResult.ok()
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="account")
+        if self.action == "redact":
+            return PluginResult.ok(new_payload, account=sorted(set(findings)))
+        return PluginResult.ok(account=sorted(set(findings)))  # audit: annotate only
+
+    tool_pre_invoke = _apply
+    prompt_pre_fetch = _apply
+
+
 class SchemaGuardPlugin(Plugin):
     """Validate args/results against the tool's JSON schema (reference: schema_guard.py:168)."""
 
@@ -1079,6 +1185,7 @@ BUILTIN_PLUGINS = {
         EncodedExfilDetectionPlugin,
         SqlSanitizerPlugin,
         UrlReputationPlugin,
+        AccountNumberDetectionPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
