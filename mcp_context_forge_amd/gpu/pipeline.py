@@ -102,7 +102,20 @@ chain):
     plugin's own country table. Rows with a valid card or IBAN of a
     configured kind, and every span with a backslash or a non-ASCII byte,
     run the exact CPU plugin (tests/test_account_plugin.py checks the
-    containment on the CPU).
+    containment on the CPU);
+  * unicode_guard is an exact prefilter too, and the first whose kernel
+    decodes UTF-8 itself: only a backslash routes, non-ASCII traffic stays
+    on the GPU lane. In a span with no backslash every string value's bytes
+    stand verbatim between quotes, so every code point of a value is one of
+    the raw span with the same class. '"' is no word character, so no word
+    spans two values and a value's word is judged in the raw span exactly as
+    in the value. The per-span counts are sums over the values plus
+    whatever keys add: those can only add findings, and the CPU chain
+    answers such rows exactly. All outputs are integers, computed by
+    unicode.hip exactly as by ops/unicode.py with the plugin's own class
+    table. Rows with a non-zero count of a reported kind, and every span
+    with a backslash (a \\u escape may hide any code point), run the exact
+    CPU plugin.
 """
 
 from __future__ import annotations
@@ -188,6 +201,11 @@ class _IndexedUsers:
         return self.users[int(self.uidx[i])]
 
 
+# The exact raw-byte prefilters, by plugin handle (tooltable._HANDLES), in the
+# precedence of the pre-pass's timing key.
+PREFILTERS = ("secrets", "exfil", "sql", "url", "account", "unicode")
+
+
 class GpuPluginPipeline:
     def __init__(self, engine, device: str = "cuda"):
         self.engine = engine
@@ -199,7 +217,7 @@ class GpuPluginPipeline:
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
         self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
-        self.sql, self.url, self.account = h.sql, h.url, h.account
+        self.sql, self.url, self.account, self.unicode = h.sql, h.url, h.account, h.unicode
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -259,6 +277,11 @@ class GpuPluginPipeline:
         self._iban_table: Optional[hip.DeviceIbanTable] = None
         if self.account is not None:
             self._iban_table = hip.DeviceIbanTable(self.account.iban_table(), device)
+
+        # unicode_guard: its code point class ranges (unicode.hip)
+        self._unicode_table: Optional[hip.DeviceUnicodeTable] = None
+        if self.unicode is not None:
+            self._unicode_table = hip.DeviceUnicodeTable(self.unicode.class_table(), device)
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -360,6 +383,7 @@ class GpuPluginPipeline:
         self.sql_routed = 0      # requests the sql prefilter sent to the CPU chain
         self.url_routed = 0      # requests the url prefilter sent to the CPU chain
         self.account_routed = 0  # requests the account-number prefilter sent to the CPU chain
+        self.unicode_routed = 0  # requests the unicode prefilter sent to the CPU chain
         # optional per-stage wall-clock accounting (FORGE_PIPELINE_TIMING=1)
         self.timing_enabled = bool(os.environ.get("FORGE_PIPELINE_TIMING"))
         self.timing: Dict[str, float] = {}
@@ -492,7 +516,8 @@ class GpuPluginPipeline:
         fw_state = self._forward_foreign(rs, raws, user, users)
         if len(rs) and (tools.hostbound is not None or tools.secrets is not None
                         or tools.exfil is not None or tools.sql is not None
-                        or tools.url is not None or tools.account is not None):
+                        or tools.url is not None or tools.account is not None
+                        or tools.unicode is not None):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -552,7 +577,7 @@ class GpuPluginPipeline:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
         # secrets_detection / encoded_exfil_detection / sql_sanitizer /
-        # url_reputation / account_number_detection pre-pass:
+        # url_reputation / account_number_detection / unicode_guard pre-pass:
         # rows of tools one of them is active for, whose raw argument bytes MAY
         # hold a finding, leave with the host-bound rows and run the exact
         # CPU chain, plugins included
@@ -564,28 +589,12 @@ class GpuPluginPipeline:
             rows &= ~hb_mask
             return rows if rows.any() else None
 
-        sec_rows, exf_rows = plugin_rows(tools.secrets), plugin_rows(tools.exfil)
-        sql_rows, url_rows = plugin_rows(tools.sql), plugin_rows(tools.url)
-        acct_rows = plugin_rows(tools.account)
-        if (sec_rows is not None or exf_rows is not None or sql_rows is not None or url_rows is not None
-                or acct_rows is not None):
-            sec_flagged, exf_flagged, sql_flagged, url_flagged, acct_flagged = await self._raw_prepass(
-                rs.blob, rs.args_b, rs.args_e, sec_rows, exf_rows, sql_rows, url_rows, acct_rows=acct_rows)
-            if sec_flagged is not None:
-                self.secrets_routed += int(sec_flagged.sum())
-                hb_mask |= sec_flagged
-            if exf_flagged is not None:
-                self.exfil_routed += int(exf_flagged.sum())
-                hb_mask |= exf_flagged
-            if sql_flagged is not None:
-                self.sql_routed += int(sql_flagged.sum())
-                hb_mask |= sql_flagged
-            if url_flagged is not None:
-                self.url_routed += int(url_flagged.sum())
-                hb_mask |= url_flagged
-            if acct_flagged is not None:
-                self.account_routed += int(acct_flagged.sum())
-                hb_mask |= acct_flagged
+        rows = {handle: part for handle in PREFILTERS
+                for part in [plugin_rows(getattr(tools, handle))] if part is not None}
+        if rows:
+            for handle, flagged in (await self._raw_prepass(rs.blob, rs.args_b, rs.args_e, rows)).items():
+                setattr(self, handle + "_routed", getattr(self, handle + "_routed") + int(flagged.sum()))
+                hb_mask |= flagged
         if hb_mask.any():
             self.host_bound += n_bound
             await self._host_chain_rows(rs.rows[hb_mask], raws, row_user, server_id, rs.responses)
@@ -961,74 +970,75 @@ class GpuPluginPipeline:
         valid = (c[:, 1] if self.account.detect_cards else 0) + (c[:, 3] if self.account.detect_ibans else 0)
         return (valid > 0) | ((flags.cpu().numpy() & 1) != 0)
 
+    def _unicode_flags(self, out, n: int) -> np.ndarray:
+        """Unicode prefilter over hip.unicode_scan outputs: a row is flagged
+        when a count of a kind the plugin reports is non-zero, or when its
+        span holds a backslash. A non-ASCII byte alone does not flag: the
+        kernel decodes UTF-8 itself. Integer outputs, equal to the plugin's
+        own: nothing to round."""
+        counts, _kinds, _first, flags = out
+        want = [k for k in range(hip.UNICODE_SCAN_KINDS) if self.unicode.report_mask() >> k & 1]
+        return (counts.cpu().numpy()[:, want].sum(axis=1) > 0) | ((flags.cpu().numpy() & 1) != 0)
+
     async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
-                           sec_rows: Optional[np.ndarray], exf_rows: Optional[np.ndarray],
-                           sql_rows: Optional[np.ndarray] = None, url_rows: Optional[np.ndarray] = None,
-                           *, acct_rows: Optional[np.ndarray] = None
-                           ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray],
-                                      Optional[np.ndarray], Optional[np.ndarray]]:
+                           rows: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
         """secrets_detection, encoded_exfil_detection, sql_sanitizer,
-        url_reputation and account_number_detection prefilters over raw
-        argument bytes → (bool[m] or None) per plugin, True where the row
-        must run the exact CPU chain; `sec_rows` / `exf_rows` / `sql_rows` /
-        `url_rows` / `acct_rows` mark the rows of tools each plugin is active
-        for (None: not this batch). Eager, under _gpu_lock, ONE upload for
-        all: the secrets format bank (scan.hip) and one token_entropy launch
-        per alphabet, one decode_scan launch per encoding, one sql_scan
-        launch in boundary mode, one url_scan launch, one account_scan
-        launch, over the union of the marked rows; every other row gets an
-        empty span, and each verdict is masked with its own plugin's rows.
-        The blob is uploaded here and again by pass 1 on
-        purpose — folding this pre-pass into the captured pass-1 graph is a
-        later change. Timed as gp0_secrets when secrets_detection takes
-        part, else as gp0_exfil when encoded_exfil_detection does, else
-        as gp0_sql when sql_sanitizer does, else as gp0_url when
-        url_reputation does, as gp0_account when account_number_detection
+        url_reputation, account_number_detection and unicode_guard prefilters
+        over raw argument bytes. `rows` maps a plugin handle of PREFILTERS to
+        bool[m], the rows of tools that plugin is active for (a plugin that
+        takes no part in this batch is absent) → handle → bool[m], True where
+        the row must run the exact CPU chain. Eager, under _gpu_lock, ONE
+        upload for all: the secrets format bank (scan.hip) and one
+        token_entropy launch per alphabet, one decode_scan launch per
+        encoding, one sql_scan launch in boundary mode, one url_scan launch,
+        one account_scan launch, one unicode_scan launch, over the union of
+        the marked rows; every other row gets an empty span, and each verdict
+        is masked with its own plugin's rows. The blob is uploaded here and
+        again by pass 1 on purpose — folding this pre-pass into the captured
+        pass-1 graph is a later change. Timed under the key of the first
+        plugin of PREFILTERS that takes part: gp0_secrets, else gp0_exfil,
+        gp0_sql, gp0_url, gp0_account, and gp0_unicode when unicode_guard
         alone does."""
         t0 = self._tic()
         m = args_b.shape[0]
-        rows = np.zeros(m, dtype=bool)
-        for part in (sec_rows, exf_rows, sql_rows, url_rows, acct_rows):
-            if part is not None:
-                rows |= part
-        sb = np.ascontiguousarray(np.where(rows, args_b, 0).astype(np.int32))
-        se = np.ascontiguousarray(np.where(rows, args_e, 0).astype(np.int32))
+        union = np.zeros(m, dtype=bool)
+        for part in rows.values():
+            union |= part
+        sb = np.ascontiguousarray(np.where(union, args_b, 0).astype(np.int32))
+        se = np.ascontiguousarray(np.where(union, args_e, 0).astype(np.int32))
 
         def launch(data_t, beg_t, end_t):
-            mask_t = ent = dec = sq = ur = ac = None
-            if sec_rows is not None:
-                if "secrets" in self.banks:
-                    mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0]
-                ent = self._entropy_launch(data_t, beg_t, end_t)
-            if exf_rows is not None:
-                dec = self._exfil_launch(data_t, beg_t, end_t)
-            if sql_rows is not None:
-                sq = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
-            if url_rows is not None:
-                ur = hip.url_scan(data_t, beg_t, end_t, self._url_table, self.url.report_mask())
-            if acct_rows is not None:
-                ac = hip.account_scan(data_t, beg_t, end_t, self._iban_table, self.account.report_mask())
-            return mask_t, ent, dec, sq, ur, ac
+            out = {}
+            if "secrets" in rows:
+                mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0] if "secrets" in self.banks else None
+                out["secrets"] = (mask_t, self._entropy_launch(data_t, beg_t, end_t))
+            if "exfil" in rows:
+                out["exfil"] = self._exfil_launch(data_t, beg_t, end_t)
+            if "sql" in rows:
+                out["sql"] = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
+            if "url" in rows:
+                out["url"] = hip.url_scan(data_t, beg_t, end_t, self._url_table, self.url.report_mask())
+            if "account" in rows:
+                out["account"] = hip.account_scan(data_t, beg_t, end_t, self._iban_table, self.account.report_mask())
+            if "unicode" in rows:
+                out["unicode"] = hip.unicode_scan(data_t, beg_t, end_t, self._unicode_table, self.unicode.report_mask())
+            return out
 
-        _mm, _scores, (mask_t, ent, dec, sq, ur, ac) = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        sec_flagged = exf_flagged = sql_flagged = url_flagged = acct_flagged = None
-        if sec_rows is not None:
-            sec_flagged = self._entropy_flags(ent, m)
+        _mm, _scores, out = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
+        flagged: Dict[str, np.ndarray] = {}
+        if "secrets" in rows:
+            mask_t, ent = out["secrets"]
+            flagged["secrets"] = self._entropy_flags(ent, m)
             if mask_t is not None:
-                sec_flagged |= mask_t.cpu().numpy() != 0
-            sec_flagged &= sec_rows
-        if exf_rows is not None:
-            exf_flagged = self._exfil_flags(dec, m) & exf_rows
-        if sql_rows is not None:
-            sql_flagged = self._sql_flags(sq, m) & sql_rows
-        if url_rows is not None:
-            url_flagged = self._url_flags(ur, m) & url_rows
-        if acct_rows is not None:
-            acct_flagged = self._account_flags(ac, m) & acct_rows
-        self._toc("gp0_secrets" if sec_rows is not None else "gp0_exfil" if exf_rows is not None
-                  else "gp0_sql" if sql_rows is not None else "gp0_url" if url_rows is not None
-                  else "gp0_account", t0)
-        return sec_flagged, exf_flagged, sql_flagged, url_flagged, acct_flagged
+                flagged["secrets"] |= mask_t.cpu().numpy() != 0
+        for handle, flags_of in (("exfil", self._exfil_flags), ("sql", self._sql_flags), ("url", self._url_flags),
+                                 ("account", self._account_flags), ("unicode", self._unicode_flags)):
+            if handle in rows:
+                flagged[handle] = flags_of(out[handle], m)
+        for handle in flagged:
+            flagged[handle] = flagged[handle] & rows[handle]
+        self._toc("gp0_" + next(h for h in PREFILTERS if h in rows), t0)
+        return flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
         if self._slot_store:
@@ -1737,7 +1747,7 @@ class GpuPluginPipeline:
             "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
             "exfil_routed": self.exfil_routed,
             "sql_routed": self.sql_routed, "url_routed": self.url_routed,
-            "account_routed": self.account_routed,
+            "account_routed": self.account_routed, "unicode_routed": self.unicode_routed,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,
             "rescore_native": self.rescore_native, "rescore_eager": self.rescore_eager,

@@ -42,7 +42,8 @@ _HANDLES = {"deny": "deny_filter", "harm": "harmful_content_detector", "pii": "p
             "out_guard": "output_length_guard", "exact_cache": "cached_tool_result",
             "breaker": "circuit_breaker", "secrets": "secrets_detection",
             "exfil": "encoded_exfil_detection", "sql": "sql_sanitizer",
-            "url": "url_reputation", "account": "account_number_detection"}
+            "url": "url_reputation", "account": "account_number_detection",
+            "unicode": "unicode_guard"}
 MODELED = frozenset(_HANDLES.values())
 
 
@@ -117,14 +118,14 @@ class _ToolMeta:
 class ToolTable:
     """One registry/plugin generation's tables. Arrays are indexed by the
     `tool_idx` that `toolmap` resolves; with no tools they hold one dummy
-    entry. `hostbound`, `secrets`, `exfil`, `sql`, `url`, `account`, `sk_tables`,
-    `schema_bank` and `graphs` are None where absent."""
+    entry. `hostbound`, `secrets`, `exfil`, `sql`, `url`, `account`, `unicode`,
+    `sk_tables`, `schema_bank` and `graphs` are None where absent."""
 
     __slots__ = ("generation", "plugins_ver", "metas", "by_name", "index", "names", "tids",
                  "schema_bank", "nest_bits", "bankset1", "graphs", "toolmap",
                  "name_blob", "name_beg", "name_end", "required", "typed", "native_kind",
                  "outschema", "thash", "semallow",
-                 "flags", "postlane", "hostbound", "secrets", "exfil", "sql", "url", "account",
+                 "flags", "postlane", "hostbound", "secrets", "exfil", "sql", "url", "account", "unicode",
                  "rw_norm", "rw_regex", "rw_deny", "rw_pii", "rw_harm", "mod_app",
                  "sk_tables", "sk_range")
 
@@ -301,7 +302,8 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     `bank_names` are the content banks that exist (only "regex" is asked)."""
     n1 = max(len(metas), 1)
     modeled_banks = {p.name for p in (h.deny, h.pii, h.regex, h.normalizer, h.moderation, h.harm,
-                                      h.schema_guard, h.secrets, h.exfil, h.sql, h.url, h.account) if p is not None}
+                                      h.schema_guard, h.secrets, h.exfil, h.sql, h.url, h.account,
+                                      h.unicode) if p is not None}
     extra_chain = [p for p in mgr.plugins
                    if p.mode != PluginMode.DISABLED and p.name not in MODELED
                    and (HookType.TOOL_PRE_INVOKE in p.hooks or HookType.TOOL_POST_INVOKE in p.hooks)]
@@ -311,7 +313,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     # rewrite/verdict lane per-tool activation (hoists the per-row
     # active/applies python calls out of the hot loops)
     (t.rw_norm, t.rw_regex, t.rw_deny, t.rw_pii, t.rw_harm, t.mod_app, sec_act, exf_act, sql_act,
-     url_act, acct_act, t.semallow) = (np.zeros(n1, dtype=bool) for _ in range(12))
+     url_act, acct_act, uni_act, t.semallow) = (np.zeros(n1, dtype=bool) for _ in range(13))
     for i, m in enumerate(metas):
         name = m.name
         m.host_chain = any(b.get("config") or (pname not in modeled_banks)
@@ -334,6 +336,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
         sql_act[i] = active(mgr, h.sql, name, block_class=False)
         url_act[i] = active(mgr, h.url, name, block_class=False)
         acct_act[i] = active(mgr, h.account, name, block_class=False)
+        uni_act[i] = active(mgr, h.unicode, name, block_class=False)
         # semcache insert allowlist (tool-level; lookups are gated by TF_CACHE)
         t.semallow[i] = bool(semcache_on and h.semcache_plugin.cacheable(name))
         # TF_NORM = "escape triggers route this tool to the host path":
@@ -382,6 +385,7 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     t.sql = sql_act if sql_act.any() else None
     t.url = url_act if url_act.any() else None
     t.account = acct_act if acct_act.any() else None
+    t.unicode = uni_act if uni_act.any() else None
 
 
 # ---- schema-key tables ----

@@ -26,6 +26,7 @@
 #define FORGE_ERR_RESCORE_BUSY 9008  /* rescore_submit: every slot is in use */
 #define FORGE_ERR_URL_SCAN 9009   /* url_scan: slot count, pool size or report_mask */
 #define FORGE_ERR_ACCOUNT_SCAN 9010   /* account_scan: report_mask */
+#define FORGE_ERR_UNICODE_SCAN 9011   /* unicode_scan: n_ranges or report_mask */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -75,6 +76,19 @@
 #define FORGE_ACCOUNT_SCAN_MIN_LEN 15
 #define FORGE_ACCOUNT_SCAN_MAX_LEN 34
 #define FORGE_ACCOUNT_SCAN_ALL_KINDS 3
+
+/* forge_unicode_scan searches a class table of up to
+ * FORGE_UNICODE_SCAN_MAX_RANGES ranges of FORGE_UNICODE_SCAN_RANGE_BYTES bytes
+ * (u32 lo, hi, kinds, script; sorted, disjoint, above ASCII), staged into LDS
+ * once per block. A range count outside 0..FORGE_UNICODE_SCAN_MAX_RANGES or a
+ * report_mask with bits outside FORGE_UNICODE_SCAN_ALL_KINDS (the
+ * FORGE_UNICODE_SCAN_KINDS kind bits: bidi, invisible, tag, variation, joiner,
+ * private, invalid, mixed script) is an argument error. ops/unicode.py has
+ * them all. */
+#define FORGE_UNICODE_SCAN_MAX_RANGES 256
+#define FORGE_UNICODE_SCAN_RANGE_BYTES 16
+#define FORGE_UNICODE_SCAN_KINDS 8
+#define FORGE_UNICODE_SCAN_ALL_KINDS 255
 
 typedef void (*forge_task_fn)(int index, void* ctx);
 
@@ -156,6 +170,20 @@ int forge_url_scan(const void* data, const void* beg, const void* end_, int batc
  * out_flags i32[batch]. */
 int forge_account_scan(const void* data, const void* beg, const void* end_, int batch,
                        const void* iban_len, int report_mask,
+                       void* out_counts, void* out_kinds, void* out_first, void* out_flags,
+                       void* stream);
+
+/* One wave per request: UTF-8 decoded strictly (an ill-formed byte is one
+ * INVALID event), every multi-byte code point classified against table
+ * (n_ranges ranges), words of ASCII [A-Za-z0-9_] and script-bearing code points
+ * judged mixed when they hold a Latin and a Greek or Cyrillic letter.
+ * out_counts i32[batch][8] (code points per kind bit, INVALID events, mixed
+ * words), out_kinds i32[batch] (the bits with a non-zero count), out_first
+ * i32[batch][2] (absolute begin, byte length of the first finding of a kind in
+ * report_mask, or -1, 0), out_flags i32[batch] (bit 0 a backslash, bit 1 a
+ * byte >= 0x80). */
+int forge_unicode_scan(const void* data, const void* beg, const void* end_, int batch,
+                       const void* table, int n_ranges, int report_mask,
                        void* out_counts, void* out_kinds, void* out_first, void* out_flags,
                        void* stream);
 

@@ -23,6 +23,11 @@ Per-plugin reference analogs (behavioral port, no code copied):
                        and mod 97, which pii_filter's 4-4-4-4 pattern cannot
                        tell from order numbers; block / redact / audit.
                        Opt-in: not in the default chain
+  unicode_guard     → text a reviewer does not see but a model reads: tag
+                       characters, bidi overrides, invisible and private-use
+                       code points, ill-formed UTF-8 and words that mix Latin
+                       with Greek or Cyrillic letters; block / strip / audit.
+                       Opt-in: not in the default chain
   schema_guard      → plugins/schema_guard (JSON-Schema arg/result validation)
   toon_encoder       → plugins/toon_encoder (JSON→TOON result compression)
   content_moderation → plugins/content_moderation (category classifier)
@@ -790,6 +795,104 @@ class AccountNumberDetectionPlugin(Plugin):
     prompt_pre_fetch = _apply
 
 
+class UnicodeGuardPlugin(Plugin):
+    """Stop text that a human reviewer does not see but a model reads: Unicode
+    tag characters ("ASCII smuggling"), bidirectional overrides ("Trojan
+    Source"), zero-width and other invisible format characters, private-use
+    code points, ill-formed UTF-8, and homoglyph words that mix Latin with
+    Greek or Cyrillic letters (ops/unicode.py; unicode.hip on the GPU path).
+    Priority 9: with account_number_detection, before deny_filter and every
+    rewriter, which is what makes the pipeline's raw-byte prefilter sound. Pre
+    hooks only.
+
+    Config: action block (default, code "unicode") | strip | audit, report
+    (kind names; default unicode.DEFAULT_REPORT — variation selectors and
+    joiners are counted but not reported, emoji and Persian or Indic text use
+    them), exempt (code points or [lo, hi] pairs cut out of the class table),
+    extra ([lo, hi, kind-or-script name] added to it), min_findings_to_block
+    (1). Strip removes every reported code point finding; a mixed word or an
+    ill-formed byte has no safe rewrite and is annotated only.
+    """
+
+    name = "unicode_guard"
+    hooks = (HookType.TOOL_PRE_INVOKE, HookType.PROMPT_PRE_FETCH)
+    priority = 9
+    gpu_capable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        from ..ops import unicode as _unicode
+
+        self._unicode = _unicode
+        self.action: str = self.config.get("action", "block")  # block | strip | audit
+        if self.action not in ("block", "strip", "audit"):
+            raise ValueError(f"unknown unicode_guard action {self.action!r}")
+        self.min_findings_to_block = int(self.config.get("min_findings_to_block", 1))
+        self._report = 0
+        for kind in self.config.get("report", _unicode.DEFAULT_REPORT):
+            if kind not in _unicode.KIND_BITS:
+                raise ValueError(f"unknown unicode_guard kind {kind!r}")
+            self._report |= _unicode.KIND_BITS[kind]
+        self._table = _unicode.compile_classes(self.config)   # raises on a bad exempt or extra entry
+
+    def class_table(self) -> bytes:
+        """The class ranges (what hip.DeviceUnicodeTable uploads)."""
+        return self._table
+
+    def report_mask(self) -> int:
+        """The kind bits that are findings under this configuration."""
+        return self._report
+
+    def find_spans(self, raw: bytes) -> List[Tuple[int, int, str]]:
+        """Every reported finding in one string's UTF-8 bytes as (beg, end, kind name), by begin."""
+        found = self._unicode.unicode_scan_reference(raw, self._table, self._report)[0]
+        return [(b, b + n, self._unicode.KIND_NAMES[kind]) for (b, n, kind) in found if kind & self._report]
+
+    def scan_payload(self, payload: Any) -> Tuple[Any, List[str]]:
+        """Synchronous scan of every string value. → (payload, findings): the
+        payload has every reported code point finding removed when action is
+        "strip" (otherwise it is returned as is); findings holds one kind name
+        per finding."""
+        findings: List[str] = []
+        strip = self.action == "strip"
+        kept_kinds = ("invalid", "mixed_script")
+
+        def fn(s: str) -> str:
+            raw = s.encode("utf-8", "surrogatepass")
+            spans = self.find_spans(raw)
+            if not spans:
+                return s
+            findings.extend(c for _b, _e, c in spans)
+            if not strip:
+                return s
+            for b, e in sorted({(b, e) for b, e, c in spans if c not in kept_kinds}, reverse=True):
+                raw = raw[:b] + raw[e:]   # right to left, so the spans before stay valid
+            return raw.decode("utf-8", "surrogatepass")
+
+        new_payload = _walk_strings(payload, fn)
+        return (new_payload if strip and findings else payload), findings
+
+    def block_reason(self, findings: List[str]) -> Optional[str]:
+        """The violation text when these findings block, else None."""
+        if self.action == "block" and findings and len(findings) >= self.min_findings_to_block:
+            return f"hidden or deceptive unicode detected: {sorted(set(findings))}"
+        return None
+
+    async def _apply(self, ctx: PluginContext) -> PluginResult:
+        new_payload, findings = self.scan_payload(ctx.args)
+        if not findings:
+            return PluginResult.ok()
+        reason = self.block_reason(findings)
+        if reason is not None:
+            return PluginResult.block(reason, code="unicode")
+        if self.action == "strip":
+            return PluginResult.ok(new_payload, unicode=sorted(set(findings)))
+        return PluginResult.ok(unicode=sorted(set(findings)))  # audit: annotate only
+
+    tool_pre_invoke = _apply
+    prompt_pre_fetch = _apply
+
+
 class SchemaGuardPlugin(Plugin):
     """Validate args/results against the tool's JSON schema (reference: schema_guard.py:168)."""
 
@@ -1186,6 +1289,7 @@ BUILTIN_PLUGINS = {
         SqlSanitizerPlugin,
         UrlReputationPlugin,
         AccountNumberDetectionPlugin,
+        UnicodeGuardPlugin,
         SchemaGuardPlugin,
         ToonEncoderPlugin,
         ContentModerationPlugin,
