@@ -145,6 +145,10 @@ class Settings(BaseModel):
     gpu_semcache_sketch_dim: int = 256
     gpu_streams: int = 2              # compute + copy overlap
     gpu_dtype: str = "bf16"
+    # decode JSON string escapes on the GPU (unescape.hip) ahead of the raw-byte
+    # prefilters, so rows with \n, \t, \\u.... stay on the GPU lane; off: such rows
+    # run the CPU chain
+    gpu_unescape: bool = False
 
     # --- native HTTP edge (C++ epoll owner loop, transports/native_edge.py) ---
     native_edge_port: int = 0         # 0 = disabled

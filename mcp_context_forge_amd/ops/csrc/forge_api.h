@@ -27,6 +27,7 @@
 #define FORGE_ERR_URL_SCAN 9009   /* url_scan: slot count, pool size or report_mask */
 #define FORGE_ERR_ACCOUNT_SCAN 9010   /* account_scan: report_mask */
 #define FORGE_ERR_UNICODE_SCAN 9011   /* unicode_scan: n_ranges or report_mask */
+#define FORGE_ERR_JSON_UNESCAPE 9012  /* json_unescape: a null output with batch > 0 */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -186,6 +187,19 @@ int forge_unicode_scan(const void* data, const void* beg, const void* end_, int 
                        const void* table, int n_ranges, int report_mask,
                        void* out_counts, void* out_kinds, void* out_first, void* out_flags,
                        void* stream);
+
+/* One wave per request: the JSON string escapes of data[beg, end) decoded into
+ * out (as large as data), request r's bytes at out[beg[r], out_end[r]); the
+ * output is never longer than the input and bytes of out outside those ranges
+ * are unspecified. Short escapes give their byte, \uXXXX its UTF-8, a surrogate
+ * pair one 4-byte sequence, a lone surrogate EF BF BD, and a malformed
+ * backslash is copied. out_end i32[batch], out_flags i32[batch] (bit 0 an
+ * escape was decoded, 1 a decoded quote, 2 a decoded or malformed backslash,
+ * 3 a malformed escape, 4 a lone surrogate, 5 a decoded U+0000, 6 a decoded
+ * code point >= 0x80); every element is written. ops/unescape.py has them
+ * all. */
+int forge_json_unescape(const void* data, const void* beg, const void* end_, int batch,
+                        void* out, void* out_end, void* out_flags, void* stream);
 
 int forge_featurize(const void* data, const void* beg, const void* end_, int batch, int dim,
                     void* out_bf16, void* out_f32, void* stream);

@@ -44,6 +44,7 @@ _API = {
     "forge_url_scan": _sig("i", "ppp i pi pl p i pppp p"),
     "forge_account_scan": _sig("i", "ppp i pi pppp p"),
     "forge_unicode_scan": _sig("i", "ppp i pii pppp p"),
+    "forge_json_unescape": _sig("i", "ppp i ppp p"),
     "forge_featurize": _sig("i", "ppp ii pp p"),
     "forge_json_guard": _sig("i", "ppp i ii pp p"),
     "forge_gemm_bt": _sig("i", "pppp iii ii p"),
@@ -445,6 +446,30 @@ def unicode_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table
         _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(table.ranges), table.n_ranges, int(report_mask),
         _ptr(counts), _ptr(kinds), _ptr(first), _ptr(flags), _stream()))
     return counts, kinds, first, flags
+
+
+def json_unescape(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor,
+                  out: Optional[Tuple[torch.Tensor, ...]] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Decode each span's JSON string escapes into a second blob, one wave per
+    request (unescape.hip; oracle ops/unescape.py json_unescape_reference).
+    → (out_blob u8, as large as data, request r's decoded bytes at
+    out_blob[beg[r]:out_end[r]]; out_end i32[B]; flags i32[B], the bits of
+    ops/unescape.py). The begin is shared with the input, so the kernels that
+    scan the result take (out_blob, beg, out_end). The kernel writes every byte
+    of those ranges and every element of out_end and flags; bytes of out_blob
+    outside them are unspecified. `out` (those three, preallocated) makes the
+    call graph-capture safe."""
+    batch = beg.numel()
+    if out is None:
+        dev = data.device
+        out = (torch.empty(max(data.numel(), 1), dtype=torch.uint8, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev),
+               torch.empty(batch, dtype=torch.int32, device=dev))
+    out_blob, out_end, flags = out
+    _check("forge_json_unescape", _load().forge_json_unescape(
+        _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(out_blob), _ptr(out_end), _ptr(flags), _stream()))
+    return out_blob, out_end, flags
 
 
 def featurize(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, dim: int,

@@ -1,0 +1,157 @@
+"""JSON unescape on the GPU: the kernel against its CPU reference byte for byte on the smallest shapes that can
+break it, and the pipeline with gpu_unescape off and on against the CPU chain. Escapes are written as raw bytes."""
+
+import asyncio
+import functools
+import json
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from mcp_context_forge_amd.ops import sql as S
+from mcp_context_forge_amd.ops import unescape as X
+from mcp_context_forge_amd.ops import unicode as U
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="no ROCm device")]
+
+# the bytes between spans belong to no request: read, they would open a pair or escape a span's first byte
+PRE = b'x\\ud83d"\\'
+NL, E9, GRIN = b"\\n", b"\\u00e9", b"\\ud83d\\ude00"      # the 2, 6 and 12-byte forms
+
+
+def _spans():
+    """[(name, span bytes)]. Chunks of 64 bytes start at the span's begin, so an offset in the span is one in a chunk."""
+    rng = random.Random(17)
+    spans = [("empty", b""), ("just_backslash", b"\\")] + [(f"ends_in_{len(t)}", b"abc" + t) for t in (b"\\", b"\\u", b"\\u12", b"\\ud83d\\ude0")]
+    spans += [(f"form{len(e)}_at_{at}", b"a" * at + e + b" b") for e in (NL, E9, GRIN) for at in range(52, 65)]
+    spans += [(f"run{k}_ends_{at}", b"a" * (at + 1 - k) + b"\\" * k + b"n z") for k in range(1, 7) for at in (62, 63, 64, 65)]
+    spans += [("high_then_nl", b"\\ud83d\\n"), ("high_then_A", b"\\ud83d\\u0041"), ("high_high_low", b"\\ud83d" + GRIN),
+              ("low_alone", b"a\\ude00b"), ("hex_cases", b"\\u00E9\\u00e9\\uD83D\\uDE00\\ud83D\\uDe00\\u20aC\\u20Ac"),
+              ("decoded_backslash", b"\\u005c \\u005C"), ("decoded_quote", b"\\u0022"), ("decoded_nul", b"a\\u0000b"),
+              ("every_short", b'\\" \\\\ \\/ \\b \\f \\n \\r \\t'), ("not_escapes", b"\\x \\U0041 \\u00g1 \\a"),
+              ("fast_path_200", b"plain bytes, no escape: " * 9), ("fast_path_shifted", b"\\u00e9" + b"b" * 194)]
+    frags = [NL, E9, GRIN, b"\\", b"\\\\", b"\\u", b"\\ud83d", b"\\ude00", b"\\u0022", b"\\/", b"\\x", b"u", b"n", b"12", b'"',
+             b"ab", b"a" * 30, b"a" * 57, b"\xc3\xa9", b"\\u12", b"\\ud83d\\ude0", b"\\u0000", b"\\u07ff", b"\\uFFFF"]
+    spans += [(f"rand{i}", b"".join(rng.choice(frags) for _ in range(rng.choice([1, 3, 8, 20])))) for i in range(150)]
+    return spans
+
+
+@functools.lru_cache(maxsize=None)
+def _corpus():
+    """→ (names, blob u8, beg i32, end i32, reference [(bytes, flags)]); one shared blob; computed once, never modified."""
+    names, chunks, beg, end, off = [], [], [], [], 0
+    for i, (name, span) in enumerate(_spans()):
+        before = b"A" * (i % 3) + PRE
+        chunks.append(before + span)
+        names.append(name)
+        beg.append(off + len(before))
+        end.append(off + len(before) + len(span))
+        off += len(before) + len(span)
+    blob = b"".join(chunks) + b"\\ude00 tail"
+    ref = tuple(X.json_unescape_reference(blob, b, e) for b, e in zip(beg, end))
+    return tuple(names), np.frombuffer(blob, dtype=np.uint8), np.asarray(beg, dtype=np.int32), np.asarray(end, dtype=np.int32), ref
+
+
+@pytest.mark.parametrize("batch", [1, 4, None])
+def test_json_unescape_matches_reference(batch):
+    from mcp_context_forge_amd.ops import hip
+
+    names, blob, beg, end, ref = _corpus()
+    n = batch or len(names)
+    assert len(names) == 231 and len(names) % 4 and sum(1 for b in beg if b % 2) > 50
+    flags_of = {name: r[1] for name, r in zip(names, ref)}      # the corpus holds what it names
+    assert flags_of["just_backslash"] == flags_of["ends_in_1"] == flags_of["ends_in_4"] == X.BAD | X.BACKSLASH
+    assert flags_of["ends_in_11"] == X.HAD_ESCAPE | X.LONE | X.NON_ASCII | X.BAD | X.BACKSLASH
+    assert flags_of["high_then_A"] == flags_of["low_alone"] == X.HAD_ESCAPE | X.LONE | X.NON_ASCII
+    assert all(flags_of[f"form{k}_at_{at}"] == X.HAD_ESCAPE | (X.NON_ASCII if k > 2 else 0) for k in (2, 6, 12) for at in range(52, 65))
+    assert all(flags_of[f"run{k}_ends_{at}"] == X.HAD_ESCAPE | (X.BACKSLASH if k > 1 else 0) for k in range(1, 7) for at in (62, 65))
+    assert flags_of["fast_path_200"] == 0 and flags_of["not_escapes"] == X.BAD | X.BACKSLASH
+    assert (flags_of["decoded_backslash"], flags_of["decoded_quote"], flags_of["decoded_nul"]) == tuple(
+        X.HAD_ESCAPE | f for f in (X.BACKSLASH, X.QUOTE, X.NUL))
+
+    data_t, beg_t, end_t = (torch.from_numpy(a[:k].copy()).cuda() for a, k in ((blob, len(blob)), (beg, n), (end, n)))
+    out = (torch.full((len(blob),), 0xAA, dtype=torch.uint8, device="cuda"),
+           torch.full((n,), -7, dtype=torch.int32, device="cuda"), torch.full((n,), -7, dtype=torch.int32, device="cuda"))
+    with pytest.raises(hip.ForgeHipError, match="9012"):
+        hip.json_unescape(data_t, beg_t, end_t, out=(None,) + out[1:])
+    assert bool((out[1] == -7).all()) and bool((out[2] == -7).all())          # nothing was launched
+    got = hip.json_unescape(data_t, beg_t, end_t, out=out)
+    torch.cuda.synchronize()
+    assert all(g is o for g, o in zip(got, out))
+    got_blob, got_end, got_flags = (g.cpu().numpy() for g in got)
+    want_end = np.array([b + len(r[0]) for b, r in zip(beg[:n], ref)], dtype=np.int32)
+    assert np.array_equal(got_end, want_end), [names[i] for i in np.nonzero(got_end != want_end)[0]][:10]
+    assert np.array_equal(got_flags, [r[1] for r in ref[:n]]), [names[i] for i in np.nonzero(got_flags != [r[1] for r in ref[:n]])[0]][:10]
+    # every span's bytes are its own output: a neighbour that wrote past its range would show here
+    bad = [names[i] for i in range(n) if got_blob[beg[i]:want_end[i]].tobytes() != ref[i][0]]
+    assert bad == [], bad[:10]
+    owned = np.zeros(len(blob), dtype=bool)
+    for b, e in zip(beg[:n], end[:n]):
+        owned[b:e] = True
+    assert bool((got_blob[~owned] == 0xAA).all())                            # no byte outside the requests' spans was written
+
+    empty = torch.zeros(0, dtype=torch.int32, device="cuda")
+    res = hip.json_unescape(data_t, empty, empty)                                 # the empty batch
+    assert res[0].numel() == len(blob) and res[1].numel() == 0 and res[2].numel() == 0
+
+
+# tool arguments as raw JSON; the request id is the index
+TRAFFIC = [b'{"q":"plain benign payload"}', b'{"q":"SELECT a\\nFROM t\\tWHERE x = 1"}', b'{"q":"DROP\\nTABLE users"}',
+           b'{"q":"DELETE FROM t -- x\\nWHERE id = 1"}', b'{"q":"say \\"hi\\""}', b'{"q":"C:\\\\dir"}', b'{"q":"\\u202Eevil"}',
+           b'{"q":"caf\\u00e9"}', b'{"q":"\\ud83d\\ude00 ok"}', b'{"q":"\\ud83d alone"}']
+
+
+async def _build(gpu, unescape, with_sql):
+    from mcp_context_forge_amd.config import Settings
+    from mcp_context_forge_amd.engine import GatewayEngine
+    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
+    from mcp_context_forge_amd.services.upstream import make_fake_time_upstream
+
+    settings = Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
+                        gpu_enabled=gpu, gpu_semcache_capacity=1024, gpu_unescape=unescape)
+    specs = default_chain_specs() + ([{"name": "sql_sanitizer"}] if with_sql else []) + [{"name": "unicode_guard"}]
+    e = GatewayEngine(settings, plugin_manager=load_plugin_manager(specs=specs))
+    await e.gateway_service.register_gateway(name="fast-time", url="inproc://t", client=make_fake_time_upstream())
+    if gpu:
+        assert e.enable_gpu()
+    return e
+
+
+async def _both(unescape, with_sql):
+    """CPU engine and GPU engine over the traffic → (rows the references flag per plugin, GPU stats)."""
+    cpu, gpu = await _build(False, unescape, with_sql), await _build(True, unescape, with_sql)
+    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"fast-time-echo","arguments":%s}}' % (i, a)
+            for i, a in enumerate(TRAFFIC)]
+    cpu_out, gpu_out = await cpu.process_rpc_batch(list(raws)), await gpu.process_rpc_batch(list(raws))
+    for i, (c, g) in enumerate(zip(cpu_out, gpu_out)):
+        assert json.loads(c) == json.loads(g), (i, c, g)
+    uni, sql = cpu.plugins.get("unicode_guard"), cpu.plugins.get("sql_sanitizer")
+    flagged = {"unicode": [], "sql": []}
+    for i, args in enumerate(TRAFFIC):
+        span, flags = X.json_unescape_reference(args, 0, len(args)) if unescape else (args, 0)
+        route = bool(flags & X.ROUTE_MASK)
+        _f, counts, _k, _first, uflags = U.unicode_scan_reference(span, uni.class_table(), uni.report_mask())
+        if route or uflags & 1 or any(counts[k] for k in range(U.N_KINDS) if uni.report_mask() >> k & 1):
+            flagged["unicode"].append(i)
+        if sql is not None:
+            _f, _c, counts, mask, _first, sflags = S.sql_scan_reference(span, sql.keyword_tables(), sql.keyword_lengths(), True)
+            if route or sflags & 1 or mask or (counts[1] and sql.block_delete_without_where) or \
+               (counts[2] and sql.block_update_without_where) or (counts[3] and sql.strip_comments):
+                flagged["sql"].append(i)
+    stats = gpu.gpu_pipeline.stats()
+    await cpu.shutdown()
+    await gpu.shutdown()
+    return flagged, stats
+
+
+@pytest.mark.parametrize("with_sql", [False, True], ids=["unicode", "unicode_sql"])
+@pytest.mark.parametrize("unescape", [False, True], ids=["off", "on"])
+def test_pipeline_unescape_parity(unescape, with_sql):
+    flagged, st = asyncio.run(_both(unescape, with_sql))
+    # off: every row with a backslash leaves the lane. on: only what the decoded bytes give cause for
+    assert flagged["unicode"] == ([4, 5, 6, 9] if unescape else list(range(1, 10)))
+    assert flagged["sql"] == ([] if not with_sql else [2, 4, 5, 6, 7, 8, 9] if unescape else list(range(1, 10)))
+    assert st["unicode_routed"] == len(flagged["unicode"]) and st["sql_routed"] == len(flagged["sql"])
+    assert st["unescape_rows"] == (9 if unescape else 0) and st["host_bound"] == 0
