@@ -24,6 +24,10 @@ __device__ __forceinline__ float bf16_to_f(short s) {
 __device__ __forceinline__ short f_to_bf16(float f) {
     union { float f; uint32_t u; } cvt;
     cvt.f = f;
+    // NaN: the rounding add below would carry a low-mantissa payload away
+    // (-> Inf) or wrap an all-ones mantissa into the sign (-> -0). Keep the
+    // sign and the high payload, set the quiet bit.
+    if ((cvt.u & 0x7fffffffu) > 0x7f800000u) return (short)((cvt.u >> 16) | 0x0040u);
     // round-to-nearest-even
     uint32_t lsb = (cvt.u >> 16) & 1;
     cvt.u += 0x7fff + lsb;

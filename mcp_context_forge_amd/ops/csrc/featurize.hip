@@ -88,6 +88,7 @@ extern "C" int forge_featurize(
     const void* data, const void* beg, const void* end_, int batch, int dim,
     void* out_bf16, void* out_f32, void* stream)
 {
+    if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     size_t lds = (size_t)dim * 4;
     hipLaunchKernelGGL(featurize_kernel, dim3(batch), dim3(256), lds, s,

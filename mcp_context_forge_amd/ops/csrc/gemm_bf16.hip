@@ -162,6 +162,7 @@ extern "C" int forge_gemv_head(
     int M, int C, int K, int act, void* stream)
 {
     if (K % (WAVE * 8)) return FORGE_ERR_GEMV_K;
+    if (M <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     int waves_per_block = 256 / WAVE;
     int grid = ceil_div(M, waves_per_block);
@@ -231,6 +232,7 @@ extern "C" int forge_rows_argmax_merge(
     const void* scores, int M, int Nc, int idx_base, const void* valid,
     void* best_val, void* best_idx, void* stream)
 {
+    if (M <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     int waves_per_block = 256 / WAVE;
     int grid = ceil_div(M, waves_per_block);

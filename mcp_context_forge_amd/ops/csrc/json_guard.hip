@@ -68,6 +68,7 @@ extern "C" int forge_json_guard(
     const void* data, const void* beg, const void* end_, int batch, int max_depth, int max_string,
     void* out_status, void* out_depth, void* stream)
 {
+    if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     int block = 256;
     hipLaunchKernelGGL(json_guard_kernel, dim3(ceil_div(batch, block)), dim3(block), 0, s,

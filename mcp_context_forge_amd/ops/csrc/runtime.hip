@@ -33,6 +33,7 @@ extern "C" int forge_rows_gather_scatter_bf16(
     void* valid, int R, int D, void* stream)
 {
     if (D % 8) return FORGE_ERR_ROW_ALIGN;
+    if (R <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(rows_gather_scatter_bf16_kernel, dim3(R), dim3(256), 0, s,
                        (const short*)src, (const int32_t*)src_rows, (const int32_t*)dst_slots,
@@ -66,6 +67,7 @@ extern "C" int forge_verify_dot(
     int M, int D, void* stream)
 {
     if (D % 8) return FORGE_ERR_ROW_ALIGN;
+    if (M <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(verify_dot_kernel, dim3((M + 3) / 4), dim3(256), 0, s,
                        (const short*)feats, (const short*)keys,

@@ -150,6 +150,7 @@ extern "C" int forge_scan(
     int n_states, int n_classes,
     void* out_mask, void* out_first_end, void* stream)
 {
+    if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     int block = 256;
     int grid = ceil_div(batch, block);
