@@ -55,16 +55,28 @@ def median_ms(fn, iters: int, warmup: int = 10) -> float:
     return statistics.median(times)
 
 
-async def prepass_ms(spans, batches: int) -> float:
+def pack_spans(spans):
+    """The spans back to back on the device → (data_t u8, beg_t i32[n], end_t i32[n], lens np.int32[n])."""
+    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
+    end = np.cumsum(lens).astype(np.int32)
+    beg = (end - lens).astype(np.int32)
+    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
+    return data_t, torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda(), lens
+
+
+async def prepass_ms(specs, handle: str, spans, batches: int, **settings):
+    """`batches` batches of one tools/call per span through an engine whose chain is the default one plus the
+    plugin `specs`, after one warm-up batch → (the pre-pass's wall ms per batch under "gp0_" + handle, the
+    change of every integer stats() counter per batch). `settings` are further Settings fields."""
     os.environ["FORGE_PIPELINE_TIMING"] = "1"
     from mcp_context_forge_amd.config import Settings
     from mcp_context_forge_amd.engine import GatewayEngine
     from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
     from mcp_context_forge_amd.services.upstream import NativeInProcUpstream
 
-    specs = default_chain_specs() + [{"name": "secrets_detection"}]
     e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
-                               gpu_enabled=True), plugin_manager=load_plugin_manager(specs=specs))
+                               gpu_enabled=True, **settings),
+                      plugin_manager=load_plugin_manager(specs=default_chain_specs() + specs))
     await e.gateway_service.register_gateway(name="native-time", url="inproc://n", client=NativeInProcUpstream())
     assert e.enable_gpu()
     raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"native-time-echo","arguments":%s}}'
@@ -72,12 +84,13 @@ async def prepass_ms(spans, batches: int) -> float:
     await e.process_rpc_batch(list(raws))   # warm-up
     pipe = e.gpu_pipeline
     pipe.timing.clear()
+    before = pipe.stats()
     for _ in range(batches):
         await e.process_rpc_batch(list(raws))
-    ms = pipe.timing["gp0_secrets"] / batches * 1e3
-    routed = pipe.stats()["secrets_routed"]
+    after = pipe.stats()
+    ms = pipe.timing["gp0_" + handle] / batches * 1e3
     await e.shutdown()
-    return ms, routed
+    return ms, {k: (v - before[k]) // batches for k, v in after.items() if isinstance(v, int)}
 
 
 def main() -> None:
@@ -92,11 +105,7 @@ def main() -> None:
     from mcp_context_forge_amd.plugins.builtin import SecretsDetectionPlugin
 
     spans = make_spans(a.requests, a.span)
-    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
-    end = np.cumsum(lens).astype(np.int32)
-    beg = (end - lens).astype(np.int32)
-    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
-    beg_t, end_t = torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda()
+    data_t, beg_t, end_t, lens = pack_spans(spans)
     plugin = SecretsDetectionPlugin()
     bank = hip.DeviceScanTables(plugin.scan_tables())
     sym = hip.entropy_table(hip.ENTROPY_BASE64())
@@ -109,9 +118,9 @@ def main() -> None:
         "scan_secrets_bank_ms": round(median_ms(lambda: hip.scan(data_t, beg_t, end_t, bank), a.iters), 4),
         "bank_states": bank.n_states,
     }
-    ms, routed = asyncio.run(prepass_ms(spans, a.batches))
+    ms, delta = asyncio.run(prepass_ms([{"name": "secrets_detection"}], "secrets", spans, a.batches))
     res["gp0_secrets_ms_per_batch"] = round(ms, 3)
-    res["secrets_routed"] = routed
+    res["secrets_routed"] = delta["secrets_routed"] * (a.batches + 1)   # the counter's total, warm-up batch included
     print(json.dumps(res))
 
 

@@ -16,13 +16,11 @@ from __future__ import annotations
 import argparse
 import asyncio
 import json
-import os
 import random
 
-import numpy as np
 import torch
 
-from entropy_bench import make_spans, median_ms   # same directory: sets up sys.path for the package too
+from entropy_bench import make_spans, median_ms, pack_spans, prepass_ms   # same directory: sets up sys.path for the package too
 
 
 def add_sql(spans, share: float, seed: int = 3):
@@ -43,32 +41,6 @@ def add_sql(spans, share: float, seed: int = 3):
     return out
 
 
-async def prepass_ms(spans, batches: int):
-    os.environ["FORGE_PIPELINE_TIMING"] = "1"
-    from mcp_context_forge_amd.config import Settings
-    from mcp_context_forge_amd.engine import GatewayEngine
-    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
-    from mcp_context_forge_amd.services.upstream import NativeInProcUpstream
-
-    specs = default_chain_specs() + [{"name": "sql_sanitizer"}]
-    e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
-                               gpu_enabled=True), plugin_manager=load_plugin_manager(specs=specs))
-    await e.gateway_service.register_gateway(name="native-time", url="inproc://n", client=NativeInProcUpstream())
-    assert e.enable_gpu()
-    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"native-time-echo","arguments":%s}}'
-            % (i, s) for i, s in enumerate(spans)]
-    await e.process_rpc_batch(list(raws))   # warm-up
-    pipe = e.gpu_pipeline
-    pipe.timing.clear()
-    routed0 = pipe.stats()["sql_routed"]
-    for _ in range(batches):
-        await e.process_rpc_batch(list(raws))
-    ms = pipe.timing["gp0_sql"] / batches * 1e3
-    routed = (pipe.stats()["sql_routed"] - routed0) // batches
-    await e.shutdown()
-    return ms, routed
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=8192)
@@ -83,11 +55,7 @@ def main() -> None:
                                                        SqlSanitizerPlugin)
 
     spans = add_sql(make_spans(a.requests, a.span), a.share)
-    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
-    end = np.cumsum(lens).astype(np.int32)
-    beg = (end - lens).astype(np.int32)
-    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
-    beg_t, end_t = torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda()
+    data_t, beg_t, end_t, lens = pack_spans(spans)
     plugin, exfil = SqlSanitizerPlugin(), EncodedExfilDetectionPlugin()
     kw = hip.DeviceScanTables(plugin.keyword_tables())
     kw_len = torch.tensor(plugin.keyword_lengths(), dtype=torch.int32, device="cuda")
@@ -117,9 +85,9 @@ def main() -> None:
         "sql_scan_boundary_ms": round(median_ms(lambda: sql(True, sql_out[True]), a.iters), 4),
         "sql_scan_text_ms": round(median_ms(lambda: sql(False, sql_out[False]), a.iters), 4),
     }
-    ms, routed = asyncio.run(prepass_ms(spans, a.batches))
+    ms, delta = asyncio.run(prepass_ms([{"name": "sql_sanitizer"}], "sql", spans, a.batches))
     res["gp0_sql_ms_per_batch"] = round(ms, 3)
-    res["sql_routed_per_batch"] = routed
+    res["sql_routed_per_batch"] = delta["sql_routed"]
     print(json.dumps(res))
 
 

@@ -19,13 +19,11 @@ from __future__ import annotations
 import argparse
 import asyncio
 import json
-import os
 import random
 
-import numpy as np
 import torch
 
-from entropy_bench import make_spans, median_ms   # same directory: sets up sys.path for the package too
+from entropy_bench import make_spans, median_ms, pack_spans, prepass_ms   # same directory: sets up sys.path for the package too
 
 STAY = ["SELECT id, name\nFROM users\nWHERE id = 7\n\tAND active = 1", "Summarise this:\n\n- first point\n- second point\n",
         "col_a\tcol_b\tcol_c\r\n1\t2\t3\r\n", "line one\nline two\nline three", "UPDATE t\nSET a = 1\nWHERE id = 2",
@@ -50,33 +48,6 @@ def add_escapes(spans, share: float, seed: int = 5):
     return out
 
 
-async def prepass_ms(spans, batches: int, unescape: bool):
-    os.environ["FORGE_PIPELINE_TIMING"] = "1"
-    from mcp_context_forge_amd.config import Settings
-    from mcp_context_forge_amd.engine import GatewayEngine
-    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
-    from mcp_context_forge_amd.services.upstream import NativeInProcUpstream
-
-    specs = default_chain_specs() + [{"name": "sql_sanitizer"}, {"name": "unicode_guard"}]
-    e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
-                               gpu_enabled=True, gpu_unescape=unescape), plugin_manager=load_plugin_manager(specs=specs))
-    await e.gateway_service.register_gateway(name="native-time", url="inproc://n", client=NativeInProcUpstream())
-    assert e.enable_gpu()
-    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"native-time-echo","arguments":%s}}'
-            % (i, s) for i, s in enumerate(spans)]
-    await e.process_rpc_batch(list(raws))   # warm-up
-    pipe = e.gpu_pipeline
-    pipe.timing.clear()
-    before = pipe.stats()
-    for _ in range(batches):
-        await e.process_rpc_batch(list(raws))
-    after = pipe.stats()
-    per_batch = {k: (after[k] - before[k]) // batches for k in ("sql_routed", "unicode_routed", "unescape_rows")}
-    ms = pipe.timing["gp0_sql"] / batches * 1e3
-    await e.shutdown()
-    return ms, per_batch
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=8192)
@@ -91,11 +62,7 @@ def main() -> None:
     from mcp_context_forge_amd.plugins.builtin import SecretsDetectionPlugin
 
     spans = add_escapes(make_spans(a.requests, a.span), a.share)
-    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
-    end = np.cumsum(lens).astype(np.int32)
-    beg = (end - lens).astype(np.int32)
-    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
-    beg_t, end_t = torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda()
+    data_t, beg_t, end_t, lens = pack_spans(spans)
     b64 = hip.entropy_table(hip.ENTROPY_BASE64())
     ent_min_len = SecretsDetectionPlugin().min_len
 
@@ -108,15 +75,16 @@ def main() -> None:
         "rows_with_escape": int(((flags & X.HAD_ESCAPE) != 0).sum()),
         "rows_route_mask": int(((flags & X.ROUTE_MASK) != 0).sum()),
         "rows_decoded_non_ascii": int(((flags & X.NON_ASCII) != 0).sum()),
-        "bytes_in": int(lens.sum()), "bytes_out": int((une_out[1].cpu().numpy() - beg).sum()),
+        "bytes_in": int(lens.sum()), "bytes_out": int((une_out[1] - beg_t).sum()),
         "token_entropy_ms": round(median_ms(
             lambda: hip.token_entropy(data_t, beg_t, end_t, b64, ent_min_len, out=ent_out), a.iters), 4),
         "json_unescape_ms": round(median_ms(lambda: hip.json_unescape(data_t, beg_t, end_t, out=une_out), a.iters), 4),
     }
     for name, on in (("off", False), ("on", True)):
-        ms, per_batch = asyncio.run(prepass_ms(spans, a.batches, on))
+        ms, delta = asyncio.run(prepass_ms([{"name": "sql_sanitizer"}, {"name": "unicode_guard"}], "sql", spans, a.batches,
+                                           gpu_unescape=on))
         res[f"gp0_sql_ms_per_batch_{name}"] = round(ms, 3)
-        res[f"per_batch_{name}"] = per_batch
+        res[f"per_batch_{name}"] = {k: delta[k] for k in ("sql_routed", "unicode_routed", "unescape_rows")}
     print(json.dumps(res))
 
 

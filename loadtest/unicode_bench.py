@@ -17,13 +17,11 @@ from __future__ import annotations
 import argparse
 import asyncio
 import json
-import os
 import random
 
-import numpy as np
 import torch
 
-from entropy_bench import make_spans, median_ms   # same directory: sets up sys.path for the package too
+from entropy_bench import make_spans, median_ms, pack_spans, prepass_ms   # same directory: sets up sys.path for the package too
 
 BENIGN = ["café crème brûlée à la carte", "привет мир, как дела сегодня",
           "東京都渋谷区 会議室", "Ελληνικά και λατινικά"]
@@ -45,32 +43,6 @@ def add_unicode(spans, share: float, seed: int = 5):
     return out
 
 
-async def prepass_ms(spans, batches: int):
-    os.environ["FORGE_PIPELINE_TIMING"] = "1"
-    from mcp_context_forge_amd.config import Settings
-    from mcp_context_forge_amd.engine import GatewayEngine
-    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
-    from mcp_context_forge_amd.services.upstream import NativeInProcUpstream
-
-    specs = default_chain_specs() + [{"name": "unicode_guard"}]
-    e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
-                               gpu_enabled=True), plugin_manager=load_plugin_manager(specs=specs))
-    await e.gateway_service.register_gateway(name="native-time", url="inproc://n", client=NativeInProcUpstream())
-    assert e.enable_gpu()
-    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"native-time-echo","arguments":%s}}'
-            % (i, s) for i, s in enumerate(spans)]
-    await e.process_rpc_batch(list(raws))   # warm-up
-    pipe = e.gpu_pipeline
-    pipe.timing.clear()
-    routed0 = pipe.stats()["unicode_routed"]
-    for _ in range(batches):
-        await e.process_rpc_batch(list(raws))
-    ms = pipe.timing["gp0_unicode"] / batches * 1e3
-    routed = (pipe.stats()["unicode_routed"] - routed0) // batches
-    await e.shutdown()
-    return ms, routed
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=8192)
@@ -86,11 +58,7 @@ def main() -> None:
     from mcp_context_forge_amd.plugins.builtin import SecretsDetectionPlugin, UnicodeGuardPlugin
 
     spans = add_unicode(make_spans(a.requests, a.span), a.share)
-    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
-    end = np.cumsum(lens).astype(np.int32)
-    beg = (end - lens).astype(np.int32)
-    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
-    beg_t, end_t = torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda()
+    data_t, beg_t, end_t, lens = pack_spans(spans)
     b64 = hip.entropy_table(hip.ENTROPY_BASE64())
     ent_min_len = SecretsDetectionPlugin().min_len
     iban_table = hip.DeviceIbanTable(A.compile_iban_lengths())
@@ -115,9 +83,9 @@ def main() -> None:
         "unicode_scan_ms": round(median_ms(
             lambda: hip.unicode_scan(data_t, beg_t, end_t, table, mask, out=uni_out), a.iters), 4),
     }
-    ms, routed = asyncio.run(prepass_ms(spans, a.batches))
+    ms, delta = asyncio.run(prepass_ms([{"name": "unicode_guard"}], "unicode", spans, a.batches))
     res["gp0_unicode_ms_per_batch"] = round(ms, 3)
-    res["unicode_routed_per_batch"] = routed
+    res["unicode_routed_per_batch"] = delta["unicode_routed"]
     print(json.dumps(res))
 
 

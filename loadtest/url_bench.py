@@ -17,13 +17,11 @@ from __future__ import annotations
 import argparse
 import asyncio
 import json
-import os
 import random
 
-import numpy as np
 import torch
 
-from entropy_bench import make_spans, median_ms   # same directory: sets up sys.path for the package too
+from entropy_bench import make_spans, median_ms, pack_spans, prepass_ms   # same directory: sets up sys.path for the package too
 
 TABLE_SIZES = {"lds": 256, "global": 4096}
 
@@ -49,33 +47,6 @@ def add_urls(spans, share: float, seed: int = 3):
     return out
 
 
-async def prepass_ms(spans, batches: int, n_domains: int):
-    os.environ["FORGE_PIPELINE_TIMING"] = "1"
-    from mcp_context_forge_amd.config import Settings
-    from mcp_context_forge_amd.engine import GatewayEngine
-    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
-    from mcp_context_forge_amd.services.upstream import NativeInProcUpstream
-
-    specs = default_chain_specs() + [{"name": "url_reputation", "config": {
-        "blocked_domains": domains(n_domains), "whitelist_domains": ["d3.allowed.test"]}}]
-    e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False,
-                               gpu_enabled=True), plugin_manager=load_plugin_manager(specs=specs))
-    await e.gateway_service.register_gateway(name="native-time", url="inproc://n", client=NativeInProcUpstream())
-    assert e.enable_gpu()
-    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"native-time-echo","arguments":%s}}'
-            % (i, s) for i, s in enumerate(spans)]
-    await e.process_rpc_batch(list(raws))   # warm-up
-    pipe = e.gpu_pipeline
-    pipe.timing.clear()
-    routed0 = pipe.stats()["url_routed"]
-    for _ in range(batches):
-        await e.process_rpc_batch(list(raws))
-    ms = pipe.timing["gp0_url"] / batches * 1e3
-    routed = (pipe.stats()["url_routed"] - routed0) // batches
-    await e.shutdown()
-    return ms, routed
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=8192)
@@ -90,11 +61,7 @@ def main() -> None:
     from mcp_context_forge_amd.plugins.builtin import SecretsDetectionPlugin, SqlSanitizerPlugin
 
     spans = add_urls(make_spans(a.requests, a.span), a.share)
-    lens = np.asarray([len(s) for s in spans], dtype=np.int32)
-    end = np.cumsum(lens).astype(np.int32)
-    beg = (end - lens).astype(np.int32)
-    data_t = torch.from_numpy(np.frombuffer(b"".join(spans), dtype=np.uint8).copy()).cuda()
-    beg_t, end_t = torch.from_numpy(beg).cuda(), torch.from_numpy(end).cuda()
+    data_t, beg_t, end_t, lens = pack_spans(spans)
     sqlp = SqlSanitizerPlugin()
     kw = hip.DeviceScanTables(sqlp.keyword_tables())
     kw_len = torch.tensor(sqlp.keyword_lengths(), dtype=torch.int32, device="cuda")
@@ -122,9 +89,10 @@ def main() -> None:
         res[f"url_scan_{k}_ms"] = round(median_ms(
             lambda: hip.url_scan(data_t, beg_t, end_t, t, mask, out=url_out[k]), a.iters), 4)
     for k, n in TABLE_SIZES.items():
-        ms, routed = asyncio.run(prepass_ms(spans, a.batches, n))
+        spec = {"name": "url_reputation", "config": {"blocked_domains": domains(n), "whitelist_domains": ["d3.allowed.test"]}}
+        ms, delta = asyncio.run(prepass_ms([spec], "url", spans, a.batches))
         res[f"gp0_url_{k}_ms_per_batch"] = round(ms, 3)
-        res[f"url_routed_{k}_per_batch"] = routed
+        res[f"url_routed_{k}_per_batch"] = delta["url_routed"]
     print(json.dumps(res))
 
 

@@ -40,82 +40,11 @@ chain):
     from canonical text only by whitespace/key order can score differently
     near the threshold. Rows with triggers are re-scored over canonical
     text on the host path;
-  * secrets_detection is an exact prefilter over raw bytes: a span with no
-    backslash and no non-ASCII byte holds every decoded string value
-    verbatim between quotes, and '"' is in no entropy alphabet, so every
-    run and every pattern match the CPU plugin can see is present
-    byte-for-byte in the raw span. The bank's DFA patterns are supersets
-    of the plugin's regexes and the entropy compare subtracts TOL (f32 vs
-    f64 rounding), so the prefilter may over-flag (keys, long integers)
-    but never under-flags. Flagged rows, and every span with a backslash
-    or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_secrets_plugin.py checks the containment on the CPU);
-  * encoded_exfil_detection is an exact prefilter in the same way. A span
-    with no backslash and no non-ASCII byte holds every string value
-    verbatim between quotes, and '"' is in neither the base64 nor the hex
-    alphabet, so every run the plugin can see is present byte for byte in
-    the raw span, with the same length, decoded bytes, printable count and
-    keyword mask — all integers, computed by exfil.hip exactly as by
-    ops/exfil.py, so nothing is subtracted. The prefilter over-flags only
-    where the raw span has runs the plugin never scans (keys, long
-    integers); it never under-flags. Flagged rows, and every span with a
-    backslash or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_exfil_plugin.py checks the containment on the CPU);
-  * sql_sanitizer is an exact prefilter in the same way. A span with no
-    backslash and no non-ASCII byte holds every string value verbatim
-    between quotes, and no such value contains '"'. sql.hip scans the raw
-    span in boundary mode, where every '"' resets the lexer to CODE and
-    closes the statement, so each value is lexed, matched and folded from
-    a fresh state exactly as the plugin scans it alone in text mode, and
-    the per-span counts are sums (the blocked mask an OR) over the values
-    plus whatever keys and bare literals add: they can only add findings.
-    All outputs are integers, computed by sql.hip exactly as by ops/sql.py.
-    Rows with a delete / update without where the plugin blocks, a blocked
-    word, a comment when strip_comments is on, and every span with a
-    backslash or a non-ASCII byte, run the exact CPU plugin
-    (tests/test_sql_plugin.py checks the containment on the CPU);
-  * url_reputation is an exact prefilter in the same way. A span with no
-    backslash and no non-ASCII byte holds every string value verbatim
-    between quotes. '"' is a terminator and no scheme character, so every
-    URL of a value stands in the raw span with the same "://", the same
-    scheme (the opening quote ends the look-behind where the value began),
-    the same authority end (the closing quote stands where the value
-    ended), hence the same host, the same bits and the same table lookups.
-    Each URL is judged on its own and the per-span counts are sums (the
-    mask an OR) over the values plus whatever keys add: keys can only add
-    URLs. All outputs are integers, computed by url.hip exactly as by
-    ops/url.py with the plugin's own report mask. Rows with a reported URL,
-    and every span with a backslash or a non-ASCII byte, run the exact CPU
-    plugin (tests/test_url_plugin.py checks the containment on the CPU);
-  * account_number_detection is an exact prefilter in the same way. In a
-    span with no backslash and no non-ASCII byte every string value stands
-    verbatim between quotes. '"' is not a digit, a separator, a letter, '_'
-    or '.', so it judges every boundary exactly as a string edge does: a
-    card run of a value is the same run in the raw span, with the same
-    digits, the same verdicts on the bytes before and after it and the
-    same Luhn sum, and an IBAN start of a value is one in the raw span,
-    whose walk stops where the value ends. Findings do not consume one
-    another and the per-span counts are sums over the values plus whatever
-    keys and bare numbers add: those can only add candidates. So the
-    prefilter may over-flag and never under-flags. All outputs are
-    integers, computed by account.hip exactly as by ops/account.py with the
-    plugin's own country table. Rows with a valid card or IBAN of a
-    configured kind, and every span with a backslash or a non-ASCII byte,
-    run the exact CPU plugin (tests/test_account_plugin.py checks the
-    containment on the CPU);
-  * unicode_guard is an exact prefilter too, and the first whose kernel
-    decodes UTF-8 itself: only a backslash routes, non-ASCII traffic stays
-    on the GPU lane. In a span with no backslash every string value's bytes
-    stand verbatim between quotes, so every code point of a value is one of
-    the raw span with the same class. '"' is no word character, so no word
-    spans two values and a value's word is judged in the raw span exactly as
-    in the value. The per-span counts are sums over the values plus
-    whatever keys add: those can only add findings, and the CPU chain
-    answers such rows exactly. All outputs are integers, computed by
-    unicode.hip exactly as by ops/unicode.py with the plugin's own class
-    table. Rows with a non-zero count of a reported kind, and every span
-    with a backslash (a \\u escape may hide any code point), run the exact
-    CPU plugin;
+  * secrets_detection, encoded_exfil_detection, sql_sanitizer,
+    url_reputation, account_number_detection and unicode_guard are exact
+    prefilters over raw bytes: each may over-flag and never under-flags,
+    and a flagged row runs the exact CPU chain, plugins included. Each
+    class of gpu/prefilters.py states why its rule is exact;
   * with gpu_unescape on, a backslash alone routes for none of the six.
     unescape.hip decodes the JSON escapes of each span into a second blob
     first (ops/unescape.py states the walk), and the six kernels and the
@@ -152,7 +81,6 @@ import torch
 
 from ..models.classifier import category_names
 from ..ops import dfa, hip, unescape
-from ..ops.entropy import TOL as ENTROPY_TOL
 from ..ops.pybridge import get as _pb_get
 from ..plugins.builtin import PII_PATTERNS, _text_of, _walk_strings
 from ..plugins.framework import PluginMode
@@ -162,6 +90,7 @@ from ..utils.jsonschema import validate as _validate
 from .batch import pack_texts
 from .classifier import GpuClassifier
 from .graphs import Pass1Graphs, Pass3Graphs
+from .prefilters import PREFILTERS
 from .rowset import (BAD_ARGS, INVALID_ARGS, RowSet, msg_deny, msg_harm, msg_moderation, msg_pii,
                      msg_pii_bits, msg_schema)
 from .semcache import GpuSemanticCache, tool_hash
@@ -221,11 +150,6 @@ class _IndexedUsers:
         return self.users[int(self.uidx[i])]
 
 
-# The exact raw-byte prefilters, by plugin handle (tooltable._HANDLES), in the
-# precedence of the pre-pass's timing key.
-PREFILTERS = ("secrets", "exfil", "sql", "url", "account", "unicode")
-
-
 class GpuPluginPipeline:
     def __init__(self, engine, device: str = "cuda"):
         self.engine = engine
@@ -237,7 +161,6 @@ class GpuPluginPipeline:
         self.normalizer, self.moderation, self.schema_guard = h.normalizer, h.moderation, h.schema_guard
         self.semcache_plugin, self.exact_cache, self.breaker = h.semcache_plugin, h.exact_cache, h.breaker
         self.toon, self.out_guard, self.secrets, self.exfil = h.toon, h.out_guard, h.secrets, h.exfil
-        self.sql, self.url, self.account, self.unicode = h.sql, h.url, h.account, h.unicode
 
         self.banks: Dict[str, hip.DeviceScanTables] = {}
         for name, p in (("deny", self.deny), ("harm", self.harm), ("pii", self.pii), ("regex", self.regex)):
@@ -257,51 +180,13 @@ class GpuPluginPipeline:
                     ["".join(ch if ch.isalnum() else "\\" + ch for ch in t) if not t.startswith("[") else t
                      for t in _NORMALIZE_TRIGGERS], case_insensitive=False), device)
 
-        # secrets_detection: its format bank plus one symbol table and
-        # threshold per configured entropy alphabet (entropy.hip)
-        self._secret_tabs: List[Tuple[torch.Tensor, float]] = []
-        if self.secrets is not None:
-            tables = self.secrets.scan_tables()
-            if tables is not None:
-                self.banks["secrets"] = hip.DeviceScanTables(tables, device)
-            self._secret_tabs = [(hip.entropy_table(tab, device), thr)
-                                 for (_a, _c, tab, thr) in self.secrets.entropy_detectors]
-            if not self._secret_tabs:
-                # formats only: an empty alphabet still reports the
-                # backslash / non-ASCII bit, which the prefilter needs
-                self._secret_tabs = [(hip.entropy_table(np.full(256, 0xFF, dtype=np.uint8), device),
-                                      float("inf"))]
-
-        # encoded_exfil_detection: its keyword tables plus one symbol table
-        # and symbol width per configured encoding (exfil.hip)
-        self._exfil_kw: Optional[hip.DeviceScanTables] = None
-        self._exfil_tabs: List[Tuple[torch.Tensor, int]] = []
-        if self.exfil is not None:
-            self._exfil_kw = hip.DeviceScanTables(self.exfil.keyword_tables(), device)
-            self._exfil_tabs = [(hip.entropy_table(tab, device), bits)
-                                for (_e, _c, tab, bits) in self.exfil.detectors]
-
-        # sql_sanitizer: its keyword tables and the keyword lengths (sql.hip)
-        self._sql_kw: Optional[hip.DeviceScanTables] = None
-        self._sql_kw_len: Optional[torch.Tensor] = None
-        if self.sql is not None:
-            self._sql_kw = hip.DeviceScanTables(self.sql.keyword_tables(), device)
-            self._sql_kw_len = torch.tensor(self.sql.keyword_lengths(), dtype=torch.int32, device=device)
-
-        # url_reputation: its domain table (slots, pool, powers) and report mask (url.hip)
-        self._url_table: Optional[hip.DeviceUrlTable] = None
-        if self.url is not None:
-            self._url_table = hip.DeviceUrlTable(self.url.domain_table(), device)
-
-        # account_number_detection: its country length table (account.hip)
-        self._iban_table: Optional[hip.DeviceIbanTable] = None
-        if self.account is not None:
-            self._iban_table = hip.DeviceIbanTable(self.account.iban_table(), device)
-
-        # unicode_guard: its code point class ranges (unicode.hip)
-        self._unicode_table: Optional[hip.DeviceUnicodeTable] = None
-        if self.unicode is not None:
-            self._unicode_table = hip.DeviceUnicodeTable(self.unicode.class_table(), device)
+        # the exact raw-byte prefilters of the plugins that are on, with their
+        # tables uploaded (gpu/prefilters.py); the secrets format bank also
+        # joins pass 3's bank set below
+        self.prefilters = {c.handle: c(getattr(h, c.handle), device)
+                           for c in PREFILTERS if getattr(h, c.handle) is not None}
+        if "secrets" in self.prefilters and self.prefilters["secrets"].bank is not None:
+            self.banks["secrets"] = self.prefilters["secrets"].bank
 
         self.classifier: Optional[GpuClassifier] = None
         self.feat_dim = s.gpu_feature_dim
@@ -369,14 +254,14 @@ class GpuPluginPipeline:
             dfa.compile_literals(['"structuredContent"'], case_insensitive=False), device)
 
         # fused multi-bank scans: pass 3's bank set is static; pass 1's holds
-        # the per-registry schema bank and lives in the ToolTable. With secrets
-        # or exfil on, pass 3 stays eager: token_entropy / decode_scan run on
-        # the same uploaded tensors
+        # the per-registry schema bank and lives in the ToolTable. With a
+        # prefilter that judges results (secrets, exfil) on, pass 3 stays
+        # eager: token_entropy / decode_scan run on the same uploaded tensors
         self._bankset3 = hip.ScanBankSet(
             [(n, self.banks[n]) for n in ("pii", "regex", "harm", "postmeta", "secrets")
              if n in self.banks],
             device)
-        self._graphs3 = Pass3Graphs(self) if self.secrets is None and self.exfil is None else None
+        self._graphs3 = Pass3Graphs(self) if not any(pf.post for pf in self.prefilters.values()) else None
 
         # native decision-plane stores + string tables (fastpath.cpp)
         self._slot_store = hip.store_new(self.semcache.capacity) if self.semcache is not None else 0
@@ -398,12 +283,8 @@ class GpuPluginPipeline:
         self.post_c = 0       # flagged results fully handled by forge_post_rows
         self.post_c_punt = 0  # rows the C post lane punted back to Python
         self.host_bound = 0   # requests routed to the CPU chain by plugin bindings
-        self.secrets_routed = 0  # requests the secrets prefilter sent to the CPU chain
-        self.exfil_routed = 0    # requests the encoded-exfil prefilter sent to the CPU chain
-        self.sql_routed = 0      # requests the sql prefilter sent to the CPU chain
-        self.url_routed = 0      # requests the url prefilter sent to the CPU chain
-        self.account_routed = 0  # requests the account-number prefilter sent to the CPU chain
-        self.unicode_routed = 0  # requests the unicode prefilter sent to the CPU chain
+        # requests each prefilter sent to the CPU chain, by handle
+        self.routed: Dict[str, int] = {c.handle: 0 for c in PREFILTERS}
         # gpu_unescape: the prefilters scan the spans with their JSON escapes decoded (unescape.hip)
         self.gpu_unescape = s.gpu_unescape
         self.unescape_rows = 0   # prefilter rows in which the unescape kernel decoded an escape
@@ -537,10 +418,7 @@ class GpuPluginPipeline:
                     args_b, args_e, blob, env, responses, tools, self)
 
         fw_state = self._forward_foreign(rs, raws, user, users)
-        if len(rs) and (tools.hostbound is not None or tools.secrets is not None
-                        or tools.exfil is not None or tools.sql is not None
-                        or tools.url is not None or tools.account is not None
-                        or tools.unicode is not None):
+        if len(rs) and (tools.hostbound is not None or tools.prefilter):
             await self._route_host_rows(rs, raws, row_user, server_id)
         if len(rs):
             await self._gpu_rows(rs)
@@ -599,24 +477,20 @@ class GpuPluginPipeline:
         if tools.hostbound is not None:
             hb_mask[valid] = tools.hostbound[tool_idx[valid]]
         n_bound = int(hb_mask.sum())
-        # secrets_detection / encoded_exfil_detection / sql_sanitizer /
-        # url_reputation / account_number_detection / unicode_guard pre-pass:
-        # rows of tools one of them is active for, whose raw argument bytes MAY
-        # hold a finding, leave with the host-bound rows and run the exact
-        # CPU chain, plugins included
-        def plugin_rows(per_tool: Optional[np.ndarray]) -> Optional[np.ndarray]:
-            if per_tool is None:
-                return None
+        # prefilter pre-pass: rows of tools a prefilter's plugin is active
+        # for, whose raw argument bytes MAY hold a finding, leave with the
+        # host-bound rows and run the exact CPU chain, plugins included
+        def plugin_rows(per_tool: np.ndarray) -> Optional[np.ndarray]:
             rows = np.zeros(m, dtype=bool)
             rows[valid] = per_tool[tool_idx[valid]]
             rows &= ~hb_mask
             return rows if rows.any() else None
 
-        rows = {handle: part for handle in PREFILTERS
-                for part in [plugin_rows(getattr(tools, handle))] if part is not None}
+        rows = {handle: part for handle in self.prefilters if handle in tools.prefilter
+                for part in [plugin_rows(tools.prefilter[handle])] if part is not None}
         if rows:
             for handle, flagged in (await self._raw_prepass(rs.blob, rs.args_b, rs.args_e, rows)).items():
-                setattr(self, handle + "_routed", getattr(self, handle + "_routed") + int(flagged.sum()))
+                self.routed[handle] += int(flagged.sum())
                 hb_mask |= flagged
         if hb_mask.any():
             self.host_bound += n_bound
@@ -918,113 +792,22 @@ class GpuPluginPipeline:
         toc("gpu_pass1", t_g)
         return mm, scores, ext
 
-    def _entropy_launch(self, data_t, beg_t, end_t):
-        """One token_entropy launch per configured alphabet → [(outputs, threshold)]."""
-        return [(hip.token_entropy(data_t, beg_t, end_t, tab, self.secrets.min_len), thr)
-                for tab, thr in self._secret_tabs]
-
-    def _entropy_flags(self, ent, n: int) -> np.ndarray:
-        """Secrets prefilter over hip.token_entropy outputs, one entry per
-        alphabet as ((max_h, span, n_runs, flags), threshold): a row is
-        flagged when max_h >= threshold - TOL, or when its span holds a
-        backslash or a non-ASCII byte (raw bytes may differ from the
-        decoded strings, so only the host check is exact)."""
-        out = np.zeros(n, dtype=bool)
-        for (max_h, _span, _runs, flags), thr in ent:
-            out |= max_h.cpu().numpy() >= np.float32(thr - ENTROPY_TOL)
-            out |= (flags.cpu().numpy() & 1) != 0
-        return out
-
-    def _exfil_launch(self, data_t, beg_t, end_t):
-        """One decode_scan launch per configured encoding → [(counts, kw, span, flags)]."""
-        p = self.exfil
-        return [hip.decode_scan(data_t, beg_t, end_t, tab, bits, p.min_len,
-                                p.min_printable_permille, self._exfil_kw)
-                for tab, bits in self._exfil_tabs]
-
-    def _exfil_flags(self, dec, n: int) -> np.ndarray:
-        """Encoded-exfil prefilter over hip.decode_scan outputs, one entry
-        per encoding: a row is flagged when a text run holds a keyword
-        (any text run when the plugin does not require one), or when its
-        span holds a backslash or a non-ASCII byte. Integer outputs, equal
-        to the plugin's own: nothing to round."""
-        out = np.zeros(n, dtype=bool)
-        for counts, _kw, _span, flags in dec:
-            c = counts.cpu().numpy()
-            out |= c[:, 2] > 0
-            if not self.exfil.require_keyword:
-                out |= c[:, 1] > 0
-            out |= (flags.cpu().numpy() & 1) != 0
-        return out
-
-    def _sql_flags(self, out, n: int) -> np.ndarray:
-        """SQL prefilter over hip.sql_scan outputs (boundary mode): a row is
-        flagged when it holds a delete / update without where that the
-        plugin blocks, a blocked word, a comment while strip_comments is on,
-        or when its span holds a backslash or a non-ASCII byte. Integer
-        outputs, equal to the plugin's own: nothing to round."""
-        counts, blocked, _first, flags = out
-        c = counts.cpu().numpy()
-        res = blocked.cpu().numpy() != 0
-        if self.sql.block_delete_without_where:
-            res |= c[:, 1] > 0
-        if self.sql.block_update_without_where:
-            res |= c[:, 2] > 0
-        if self.sql.strip_comments:
-            res |= c[:, 3] > 0
-        res |= (flags.cpu().numpy() & 1) != 0
-        return res
-
-    def _url_flags(self, out, n: int) -> np.ndarray:
-        """URL prefilter over hip.url_scan outputs (launched with the plugin's
-        report mask): a row is flagged when it holds a reported URL, or when
-        its span holds a backslash or a non-ASCII byte. Integer outputs,
-        equal to the plugin's own: nothing to round."""
-        counts, _mask, _first, flags = out
-        return (counts.cpu().numpy()[:, 3] > 0) | ((flags.cpu().numpy() & 1) != 0)
-
-    def _account_flags(self, out, n: int) -> np.ndarray:
-        """Account-number prefilter over hip.account_scan outputs: a row is
-        flagged when it holds a valid card or IBAN of a kind the plugin
-        reports, or when its span holds a backslash or a non-ASCII byte.
-        Integer outputs, equal to the plugin's own: nothing to round."""
-        counts, _kinds, _first, flags = out
-        c = counts.cpu().numpy()
-        valid = (c[:, 1] if self.account.detect_cards else 0) + (c[:, 3] if self.account.detect_ibans else 0)
-        return (valid > 0) | ((flags.cpu().numpy() & 1) != 0)
-
-    def _unicode_flags(self, out, n: int) -> np.ndarray:
-        """Unicode prefilter over hip.unicode_scan outputs: a row is flagged
-        when a count of a kind the plugin reports is non-zero, or when its
-        span holds a backslash. A non-ASCII byte alone does not flag: the
-        kernel decodes UTF-8 itself. Integer outputs, equal to the plugin's
-        own: nothing to round."""
-        counts, _kinds, _first, flags = out
-        want = [k for k in range(hip.UNICODE_SCAN_KINDS) if self.unicode.report_mask() >> k & 1]
-        return (counts.cpu().numpy()[:, want].sum(axis=1) > 0) | ((flags.cpu().numpy() & 1) != 0)
-
     async def _raw_prepass(self, blob: np.ndarray, args_b: np.ndarray, args_e: np.ndarray,
                            rows: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-        """secrets_detection, encoded_exfil_detection, sql_sanitizer,
-        url_reputation, account_number_detection and unicode_guard prefilters
-        over raw argument bytes. `rows` maps a plugin handle of PREFILTERS to
-        bool[m], the rows of tools that plugin is active for (a plugin that
-        takes no part in this batch is absent) → handle → bool[m], True where
-        the row must run the exact CPU chain. Eager, under _gpu_lock, ONE
-        upload for all: the secrets format bank (scan.hip) and one
-        token_entropy launch per alphabet, one decode_scan launch per
-        encoding, one sql_scan launch in boundary mode, one url_scan launch,
-        one account_scan launch, one unicode_scan launch, over the union of
-        the marked rows; every other row gets an empty span, and each verdict
-        is masked with its own plugin's rows. The blob is uploaded here and
-        again by pass 1 on purpose — folding this pre-pass into the captured
-        pass-1 graph is a later change. With gpu_unescape on, one json_unescape
-        launch comes first, every launch above scans its output blob with its
-        shorter ends, and a span with a ROUTE_MASK bit is flagged for every
-        plugin. Timed under the key of the first
-        plugin of PREFILTERS that takes part: gp0_secrets, else gp0_exfil,
-        gp0_sql, gp0_url, gp0_account, and gp0_unicode when unicode_guard
-        alone does."""
+        """The prefilters (gpu/prefilters.py, which holds each plugin's rule)
+        over raw argument bytes. `rows` maps a handle of self.prefilters to
+        bool[m], the rows of tools that plugin is active for, in PREFILTERS
+        order (a plugin that takes no part in this batch is absent) → handle
+        → bool[m], True where the row must run the exact CPU chain. Eager,
+        under _gpu_lock, ONE upload for all, then each participating
+        prefilter's launches in that order over the union of the marked rows;
+        every other row gets an empty span, and each verdict is masked with
+        its own plugin's rows. The blob is uploaded here and again by pass 1
+        on purpose — folding this pre-pass into the captured pass-1 graph is
+        a later change. With gpu_unescape on, one json_unescape launch comes
+        first, every launch above scans its output blob with its shorter
+        ends, and a span with a ROUTE_MASK bit is flagged for every plugin.
+        Timed under "gp0_" + the first participating handle."""
         t0 = self._tic()
         m = args_b.shape[0]
         union = np.zeros(m, dtype=bool)
@@ -1038,32 +821,15 @@ class GpuPluginPipeline:
             if self.gpu_unescape:
                 # every prefilter below scans the decoded blob: same begins, shorter ends
                 data_t, end_t, out["unescape"] = hip.json_unescape(data_t, beg_t, end_t)
-            if "secrets" in rows:
-                mask_t = hip.scan(data_t, beg_t, end_t, self.banks["secrets"])[0] if "secrets" in self.banks else None
-                out["secrets"] = (mask_t, self._entropy_launch(data_t, beg_t, end_t))
-            if "exfil" in rows:
-                out["exfil"] = self._exfil_launch(data_t, beg_t, end_t)
-            if "sql" in rows:
-                out["sql"] = hip.sql_scan(data_t, beg_t, end_t, self._sql_kw, self._sql_kw_len, True)
-            if "url" in rows:
-                out["url"] = hip.url_scan(data_t, beg_t, end_t, self._url_table, self.url.report_mask())
-            if "account" in rows:
-                out["account"] = hip.account_scan(data_t, beg_t, end_t, self._iban_table, self.account.report_mask())
-            if "unicode" in rows:
-                out["unicode"] = hip.unicode_scan(data_t, beg_t, end_t, self._unicode_table, self.unicode.report_mask())
+            for handle in rows:
+                pf = self.prefilters[handle]
+                # the secrets format bank is a launch of its own here, ahead of the entropy launches
+                out[handle] = pf.launch(data_t, beg_t, end_t, scan_bank=True) if handle == "secrets" \
+                    else pf.launch(data_t, beg_t, end_t)
             return out
 
         _mm, _scores, out = await self._scan_pass(None, None, blob, sb, se, m, extra=launch)
-        flagged: Dict[str, np.ndarray] = {}
-        if "secrets" in rows:
-            mask_t, ent = out["secrets"]
-            flagged["secrets"] = self._entropy_flags(ent, m)
-            if mask_t is not None:
-                flagged["secrets"] |= mask_t.cpu().numpy() != 0
-        for handle, flags_of in (("exfil", self._exfil_flags), ("sql", self._sql_flags), ("url", self._url_flags),
-                                 ("account", self._account_flags), ("unicode", self._unicode_flags)):
-            if handle in rows:
-                flagged[handle] = flags_of(out[handle], m)
+        flagged = {handle: self.prefilters[handle].flags(out[handle], m) for handle in rows}
         if "unescape" in out:
             # a span whose decoded values do not stand verbatim between their quotes routes for every plugin
             une = out["unescape"].cpu().numpy()
@@ -1072,7 +838,7 @@ class GpuPluginPipeline:
                 flagged[handle] = flagged[handle] | ((une & unescape.ROUTE_MASK) != 0)
         for handle in flagged:
             flagged[handle] = flagged[handle] & rows[handle]
-        self._toc("gp0_" + next(h for h in PREFILTERS if h in rows), t0)
+        self._toc("gp0_" + next(iter(rows)), t0)
         return flagged
 
     def _cache_result_bytes(self, slot: int) -> Optional[bytes]:
@@ -1534,25 +1300,25 @@ class GpuPluginPipeline:
         post_flag = np.zeros(n_all, dtype=bool)
         toon_meta = np.zeros(n_all, dtype=bool)
         regex3 = np.zeros(n_all, dtype=bool)
-        sec3 = None  # secrets prefilter verdict per result (secrets-active tools only)
-        exf3 = None  # encoded-exfil prefilter verdict per result (exfil-active tools only)
+        post = [pf for pf in self.prefilters.values() if pf.post]
+        pre3 = np.zeros(n_all, dtype=bool)  # prefilter verdicts per result (tools the plugin is active for only)
         if n_all:
             def pass3_extra(data_t, beg_t, end_t):
-                return (self._entropy_launch(data_t, beg_t, end_t) if self.secrets is not None else None,
-                        self._exfil_launch(data_t, beg_t, end_t) if self.exfil is not None else None)
+                return [pf.launch(data_t, beg_t, end_t) for pf in post]
 
             mm3, _scores, ext3 = await self._scan_pass(
                 self._graphs3, self._bankset3, res_blob,
                 res_beg.astype(np.int32), res_end.astype(np.int32), n_all,
                 extra=pass3_extra if self._graphs3 is None else None)
-            ent3, dec3 = ext3 or (None, None)
-            if self.secrets is not None and tools.secrets is not None:
-                sec3 = self._entropy_flags(ent3, n_all)
-                if "secrets" in self._bankset3.index:
-                    sec3 |= mm3[self._bankset3.index["secrets"]] != 0
-                sec3 &= tools.secrets[np.clip(rs.tool_idx[all_js_np], 0, None)]
-            if self.exfil is not None and tools.exfil is not None:
-                exf3 = self._exfil_flags(dec3, n_all) & tools.exfil[np.clip(rs.tool_idx[all_js_np], 0, None)]
+            for pf, out3 in zip(post, ext3 or ()):
+                if pf.handle not in tools.prefilter:
+                    continue
+                # the secrets format bank is a member of _bankset3: its mask arrives with mm3
+                if pf.handle == "secrets" and "secrets" in self._bankset3.index:
+                    hit3 = pf.flags(out3, n_all, bank_mask=mm3[self._bankset3.index["secrets"]])
+                else:
+                    hit3 = pf.flags(out3, n_all)
+                pre3 |= hit3 & tools.prefilter[pf.handle][np.clip(rs.tool_idx[all_js_np], 0, None)]
             for b, i in self._bankset3.index.items():
                 h = mm3[i] != 0
                 if b == "postmeta":
@@ -1567,11 +1333,7 @@ class GpuPluginPipeline:
         guard_max = self.out_guard.max_chars if self.out_guard is not None else 1 << 60
         outschema = tools.outschema[np.clip(rs.tool_idx[all_js_np], 0, None)] if n_all else np.zeros(0, bool)
         needs_host = post_flag | outschema | (toon_meta & (res_len >= toon_min)) | \
-            (res_len > guard_max) | err_rows.astype(bool)
-        if sec3 is not None:
-            needs_host = needs_host | sec3
-        if exf3 is not None:
-            needs_host = needs_host | exf3
+            (res_len > guard_max) | err_rows.astype(bool) | pre3
         return needs_host, regex3
 
     def _host_post_rows(self, rs: RowSet, all_js, all_js_np, host_ks, regex3, res_blob, res_beg, res_end,
@@ -1779,10 +1541,8 @@ class GpuPluginPipeline:
             "timing_s": {k: round(v, 4) for k, v in self.timing.items()} if self.timing_enabled else None,
             "batches": self.batches, "requests": self.requests, "fast_path": self.fast_path,
             "slow_path": self.slow_path, "blocked": self.blocked, "cache_hits": self.cache_hits,
-            "host_bound": self.host_bound, "secrets_routed": self.secrets_routed,
-            "exfil_routed": self.exfil_routed,
-            "sql_routed": self.sql_routed, "url_routed": self.url_routed,
-            "account_routed": self.account_routed, "unicode_routed": self.unicode_routed,
+            "host_bound": self.host_bound,
+            **{handle + "_routed": k for handle, k in self.routed.items()},
             "unescape_rows": self.unescape_rows,
             "post_rewrites": self.post_rewrites, "post_c": self.post_c,
             "post_c_punt": self.post_c_punt, "py_fallback": self.py_fallback,

@@ -17,6 +17,7 @@ import numpy as np
 
 from ..ops import dfa, hip
 from ..plugins.framework import HookType, PluginContext, PluginMode
+from .prefilters import PREFILTERS
 from .semcache import tool_hash
 
 _SCHEMA_NEST_PATTERNS = [":\\{", ":\\["]
@@ -40,10 +41,7 @@ _HANDLES = {"deny": "deny_filter", "harm": "harmful_content_detector", "pii": "p
             "moderation": "content_moderation", "semcache_plugin": "response_cache_by_prompt",
             "schema_guard": "schema_guard", "toon": "toon_encoder",
             "out_guard": "output_length_guard", "exact_cache": "cached_tool_result",
-            "breaker": "circuit_breaker", "secrets": "secrets_detection",
-            "exfil": "encoded_exfil_detection", "sql": "sql_sanitizer",
-            "url": "url_reputation", "account": "account_number_detection",
-            "unicode": "unicode_guard"}
+            "breaker": "circuit_breaker", **{c.handle: c.name for c in PREFILTERS}}
 MODELED = frozenset(_HANDLES.values())
 
 
@@ -118,14 +116,15 @@ class _ToolMeta:
 class ToolTable:
     """One registry/plugin generation's tables. Arrays are indexed by the
     `tool_idx` that `toolmap` resolves; with no tools they hold one dummy
-    entry. `hostbound`, `secrets`, `exfil`, `sql`, `url`, `account`, `unicode`,
-    `sk_tables`, `schema_bank` and `graphs` are None where absent."""
+    entry. `hostbound`, `sk_tables`, `schema_bank` and `graphs` are None where
+    absent. `prefilter` maps a handle of prefilters.PREFILTERS to bool[n_tools],
+    the tools that plugin is active for; a handle with no such tool is absent."""
 
     __slots__ = ("generation", "plugins_ver", "metas", "by_name", "index", "names", "tids",
                  "schema_bank", "nest_bits", "bankset1", "graphs", "toolmap",
                  "name_blob", "name_beg", "name_end", "required", "typed", "native_kind",
                  "outschema", "thash", "semallow",
-                 "flags", "postlane", "hostbound", "secrets", "exfil", "sql", "url", "account", "unicode",
+                 "flags", "postlane", "hostbound", "prefilter",
                  "rw_norm", "rw_regex", "rw_deny", "rw_pii", "rw_harm", "mod_app",
                  "sk_tables", "sk_range")
 
@@ -302,8 +301,8 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     `bank_names` are the content banks that exist (only "regex" is asked)."""
     n1 = max(len(metas), 1)
     modeled_banks = {p.name for p in (h.deny, h.pii, h.regex, h.normalizer, h.moderation, h.harm,
-                                      h.schema_guard, h.secrets, h.exfil, h.sql, h.url, h.account,
-                                      h.unicode) if p is not None}
+                                      h.schema_guard, *(getattr(h, c.handle) for c in PREFILTERS))
+                     if p is not None}
     extra_chain = [p for p in mgr.plugins
                    if p.mode != PluginMode.DISABLED and p.name not in MODELED
                    and (HookType.TOOL_PRE_INVOKE in p.hooks or HookType.TOOL_POST_INVOKE in p.hooks)]
@@ -312,8 +311,9 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
     postlane = np.full(n1, -1, dtype=np.int8)
     # rewrite/verdict lane per-tool activation (hoists the per-row
     # active/applies python calls out of the hot loops)
-    (t.rw_norm, t.rw_regex, t.rw_deny, t.rw_pii, t.rw_harm, t.mod_app, sec_act, exf_act, sql_act,
-     url_act, acct_act, uni_act, t.semallow) = (np.zeros(n1, dtype=bool) for _ in range(13))
+    (t.rw_norm, t.rw_regex, t.rw_deny, t.rw_pii, t.rw_harm, t.mod_app,
+     t.semallow) = (np.zeros(n1, dtype=bool) for _ in range(7))
+    pre_act = {c.handle: np.zeros(n1, dtype=bool) for c in PREFILTERS}
     for i, m in enumerate(metas):
         name = m.name
         m.host_chain = any(b.get("config") or (pname not in modeled_banks)
@@ -331,12 +331,8 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
         mod = active(mgr, h.moderation, name, block_class=True)
         harm_post = t.rw_harm[i] = bool(enforcing(h.harm) and applies(h.harm, name))
         t.mod_app[i] = applies(h.moderation, name)
-        sec_act[i] = active(mgr, h.secrets, name, block_class=False)
-        exf_act[i] = active(mgr, h.exfil, name, block_class=False)
-        sql_act[i] = active(mgr, h.sql, name, block_class=False)
-        url_act[i] = active(mgr, h.url, name, block_class=False)
-        acct_act[i] = active(mgr, h.account, name, block_class=False)
-        uni_act[i] = active(mgr, h.unicode, name, block_class=False)
+        for handle, act in pre_act.items():
+            act[i] = active(mgr, getattr(h, handle), name, block_class=False)
         # semcache insert allowlist (tool-level; lookups are gated by TF_CACHE)
         t.semallow[i] = bool(semcache_on and h.semcache_plugin.cacheable(name))
         # TF_NORM = "escape triggers route this tool to the host path":
@@ -374,18 +370,13 @@ def tool_flags(t: ToolTable, metas: List[_ToolMeta], mgr, h: PluginHandles, bank
                 pf = -1
             else:
                 pf |= 4
-        if sec_act[i] or exf_act[i]:
+        if any(pre_act[c.handle][i] for c in PREFILTERS if c.post):
             pf = -1  # flagged results need scan_payload: Python _host_post
         postlane[i] = pf
     t.flags = flags
     t.postlane = postlane
     t.hostbound = hostbound if hostbound.any() else None
-    t.secrets = sec_act if sec_act.any() else None
-    t.exfil = exf_act if exf_act.any() else None
-    t.sql = sql_act if sql_act.any() else None
-    t.url = url_act if url_act.any() else None
-    t.account = acct_act if acct_act.any() else None
-    t.unicode = uni_act if uni_act.any() else None
+    t.prefilter = {handle: act for handle, act in pre_act.items() if act.any()}
 
 
 # ---- schema-key tables ----

@@ -57,7 +57,6 @@
 
 #include "common.h"
 
-#define ACCT_WAVES 4                 // waves (= requests) per block
 #define ACCT_TABLE 676               // ops/account.py IBAN_TABLE_BYTES
 #define ACCT_POW 69                  // N_POW97
 #define ACCT_CARD 1
@@ -79,9 +78,6 @@ constexpr AcctPow acct_pow97() {
     return t;
 }
 __constant__ AcctPow ACCT_POW97 = acct_pow97();
-
-// lanes [0, n) as a mask; 0 <= n <= 64
-__device__ __forceinline__ uint64_t acct_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 
 __device__ __forceinline__ bool acct_digit(uint32_t b) { return b - '0' < 10u; }
 __device__ __forceinline__ bool acct_upper(uint32_t b) { return b - 'A' < 26u; }
@@ -126,7 +122,7 @@ __device__ __forceinline__ void acct_close(const AcctRun& run, int32_t end, uint
     if (report_mask & ACCT_CARD) acct_report(o, run.beg, end - run.beg);
 }
 
-__global__ __launch_bounds__(ACCT_WAVES * WAVE) void account_scan_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void account_scan_kernel(
     const uint8_t* __restrict__ data,    // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -146,10 +142,10 @@ __global__ __launch_bounds__(ACCT_WAVES * WAVE) void account_scan_kernel(
     __syncthreads();
 
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * ACCT_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform
     const int32_t rbeg = beg[r], rend = end_[r];
-    const uint64_t below_me = acct_below(lane);
+    const uint64_t below_me = lanes_below(lane);
 
     AcctOut o = {0, 0, 0, 0, -1, 0};
     AcctRun run = {0, 0, 0, 0, false, false};
@@ -210,7 +206,7 @@ __global__ __launch_bounds__(ACCT_WAVES * WAVE) void account_scan_kernel(
                     const int s = __builtin_ctzll(rem);
                     const uint64_t tail = ~(rem >> s);   // bit i: lane s + i is no card byte (or is past lane 63)
                     const int e = s == 0 && tail == 0 ? WAVE : s + __builtin_ctzll(tail);   // exclusive
-                    const uint64_t seg = acct_below(e) & ~acct_below(s);
+                    const uint64_t seg = lanes_below(e) & ~lanes_below(s);
                     rem &= ~seg;
                     const uint64_t dseg = digits & seg;
                     if (!(s == 0 && run.open)) {
@@ -226,7 +222,7 @@ __global__ __launch_bounds__(ACCT_WAVES * WAVE) void account_scan_kernel(
                     const int n = __builtin_popcountll(dseg);
                     if (run.digits <= 19 && (run.digits > 0 || e == WAVE || n >= 13)) {
                         // even index from the left: digits so far + digits below in the segment is even
-                        const int flip = (run.digits + __builtin_popcountll(digits & acct_below(s))) & 1;
+                        const int flip = (run.digits + __builtin_popcountll(digits & lanes_below(s))) & 1;
                         const uint64_t even = dseg & (flip ? odd_below : ~odd_below);
                         const uint64_t odd = dseg & ~even;
                         run.sum_a += acct_sum4(twice, even) + acct_sum4(plain, odd);
@@ -270,9 +266,9 @@ __global__ __launch_bounds__(ACCT_WAVES * WAVE) void account_scan_kernel(
             ++o.iban_cand;
 
             // mod 97: the symbols are the alphanumerics up to pos
-            const uint64_t sym = an & acct_below(pos + 1);
+            const uint64_t sym = an & lanes_below(pos + 1);
             const uint64_t let = sym & __ballot(acct_upper(x));
-            const uint64_t above_me = ~acct_below(lane + 1);
+            const uint64_t above_me = ~lanes_below(lane + 1);
             // decimal digits right of the lane's symbol once the four leading symbols stand last
             const int right = 6 + __builtin_popcountll(sym & above_me) + __builtin_popcountll(let & above_me);
             const int lead = lane == 0 ? 4 : lane == 1 ? 2 : lane == 2 ? 1 : 0;   // the start's four bytes are lanes 0..3
@@ -313,8 +309,8 @@ extern "C" int forge_account_scan(
     if (report_mask & ~FORGE_ACCOUNT_SCAN_ALL_KINDS) return FORGE_ERR_ACCOUNT_SCAN;
     if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int grid = ceil_div(batch, ACCT_WAVES);
-    hipLaunchKernelGGL(account_scan_kernel, dim3(grid), dim3(ACCT_WAVES * WAVE), 0, s,
+    int grid = ceil_div(batch, ROW_WAVES);
+    hipLaunchKernelGGL(account_scan_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), 0, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (const uint8_t*)iban_len, (uint32_t)report_mask,
                        (int32_t*)out_counts, (int32_t*)out_kinds, (int32_t*)out_first, (int32_t*)out_flags);

@@ -9,6 +9,10 @@
 #include "forge_api.h"
 
 #define WAVE 64  // CDNA wavefront width (hard-coded per guide: warpSize==64 on gfx950)
+#define ROW_WAVES 4  // waves (= requests) per block of the wave-per-request kernels
+
+// lanes [0, n) as a mask; n >= 64 (sql.hip passes 65) gives every lane
+__device__ __forceinline__ uint64_t lanes_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 
 // 8 x bf16 stored as shorts — the vectorized load unit (guide G13).
 typedef __attribute__((ext_vector_type(8))) short short8;

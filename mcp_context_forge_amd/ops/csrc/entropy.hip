@@ -24,9 +24,7 @@
 
 #include "common.h"
 
-#define ENTROPY_WAVES 4  // waves (= requests) per block
-
-__global__ __launch_bounds__(ENTROPY_WAVES * WAVE) void token_entropy_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void token_entropy_kernel(
     const uint8_t* __restrict__ data,   // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -44,7 +42,7 @@ __global__ __launch_bounds__(ENTROPY_WAVES * WAVE) void token_entropy_kernel(
     __syncthreads();
 
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * ENTROPY_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform
     const int32_t rbeg = beg[r], rend = end_[r];
 
@@ -119,8 +117,8 @@ extern "C" int forge_token_entropy(
 {
     if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int grid = ceil_div(batch, ENTROPY_WAVES);
-    hipLaunchKernelGGL(token_entropy_kernel, dim3(grid), dim3(ENTROPY_WAVES * WAVE), 0, s,
+    int grid = ceil_div(batch, ROW_WAVES);
+    hipLaunchKernelGGL(token_entropy_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), 0, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (const uint8_t*)sym, min_len < 1 ? 1 : min_len,
                        (float*)out_h, (int32_t*)out_span, (int32_t*)out_runs, (int32_t*)out_flags);

@@ -37,7 +37,6 @@
 
 #include "common.h"
 
-#define SQL_WAVES 4       // waves (= requests) per block
 #define SQL_LOOKAHEAD 32  // bytes after the chunk in the window (>= FORGE_SQL_SCAN_KW_MAX_LEN + 1)
 #define SQL_WIN (WAVE + SQL_LOOKAHEAD)
 #define SQL_LENMASKS 32   // keyword masks by word length, 0..31
@@ -47,15 +46,12 @@ static_assert(SQL_LOOKAHEAD >= FORGE_SQL_SCAN_KW_MAX_LEN + 1 && SQL_LENMASKS > F
 
 enum { SQL_CODE = 0, SQL_SQUOTE, SQL_DQUOTE, SQL_LINE, SQL_BLOCK };
 
-// lanes [0, n) as a mask; n may be 64 or 65
-__device__ __forceinline__ uint64_t sql_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
-
 __device__ __forceinline__ bool sql_word_char(uint32_t b) {
     const uint32_t l = b | 0x20u;
     return (b >= '0' && b <= '9') || (l >= 'a' && l <= 'z') || b == '_';
 }
 
-__global__ __launch_bounds__(SQL_WAVES * WAVE) void sql_scan_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void sql_scan_kernel(
     const uint8_t* __restrict__ data,    // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(SQL_WAVES * WAVE) void sql_scan_kernel(
     __syncthreads();
 
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * SQL_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform
     const int32_t rbeg = beg[r], rend = end_[r];
 
@@ -162,14 +158,14 @@ __global__ __launch_bounds__(SQL_WAVES * WAVE) void sql_scan_kernel(
                 case SQL_LINE: ev = nl | bq; break;
                 default: ev = bc | bq; break;
             }
-            ev &= ~sql_below(pos);
+            ev &= ~lanes_below(pos);
             if (!ev) {
-                if (state == SQL_CODE) code |= ~sql_below(pos);
+                if (state == SQL_CODE) code |= ~lanes_below(pos);
                 break;
             }
             const int t = __builtin_ctzll(ev);
             const uint64_t bit = 1ull << t;
-            if (state == SQL_CODE) code |= sql_below(t) & ~sql_below(pos);
+            if (state == SQL_CODE) code |= lanes_below(t) & ~lanes_below(pos);
             pos = t + 1;
             if (bit & bq) {                 // field boundary, in any state
                 state = SQL_CODE;
@@ -240,9 +236,9 @@ __global__ __launch_bounds__(SQL_WAVES * WAVE) void sql_scan_kernel(
             }
             int cur = 0;
             while (true) {
-                const uint64_t tt = term & ~sql_below(cur);
+                const uint64_t tt = term & ~lanes_below(cur);
                 const int e = tt ? __builtin_ctzll(tt) : WAVE;
-                const uint64_t seg = sql_below(e) & ~sql_below(cur);
+                const uint64_t seg = lanes_below(e) & ~lanes_below(cur);
                 if (kany & seg) {
                     if (st_del < 0 && (kdel & seg)) st_del = p + __builtin_ctzll(kdel & seg);
                     if (st_upd < 0 && (kupd & seg)) st_upd = p + __builtin_ctzll(kupd & seg);
@@ -285,9 +281,9 @@ extern "C" int forge_sql_scan(
         return FORGE_ERR_SQL_SCAN;
     if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int grid = ceil_div(batch, SQL_WAVES);
-    size_t lds = (size_t)FORGE_SCAN_TABLE_BYTES(n_states, n_classes) + SQL_LENMASKS * 4 + SQL_WAVES * SQL_WIN;
-    hipLaunchKernelGGL(sql_scan_kernel, dim3(grid), dim3(SQL_WAVES * WAVE), lds, s,
+    int grid = ceil_div(batch, ROW_WAVES);
+    size_t lds = (size_t)FORGE_SCAN_TABLE_BYTES(n_states, n_classes) + SQL_LENMASKS * 4 + ROW_WAVES * SQL_WIN;
+    hipLaunchKernelGGL(sql_scan_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), lds, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (const uint16_t*)next, (const uint8_t*)klass, (const uint32_t*)accept,
                        n_states, n_classes, (const int32_t*)kw_len, n_kw, kw_max_len, dquote_boundary ? 1 : 0,

@@ -57,8 +57,6 @@
 
 #include "common.h"
 
-#define UNE_WAVES 4   // waves (= requests) per block
-
 // flag bits, as ops/unescape.py
 #define UNE_HAD_ESCAPE 1
 #define UNE_QUOTE 2
@@ -71,8 +69,6 @@
 #define UNE_EVEN 0x5555555555555555ull
 #define UNE_NO_UNIT 0x10000u   // above every code unit: "not four hex digits"
 
-// lanes [0, n) as a mask; 0 <= n <= 64
-__device__ __forceinline__ uint64_t une_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 // set bits of m in the lanes below this one
 __device__ __forceinline__ int une_rank(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -89,7 +85,7 @@ __device__ __forceinline__ uint32_t une_unit(uint32_t h0, uint32_t h1, uint32_t 
 // 1 + the index of the highest set bit; 0 for 0
 __device__ __forceinline__ int une_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
 
-__global__ __launch_bounds__(UNE_WAVES * WAVE) void json_unescape_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void json_unescape_kernel(
     const uint8_t* __restrict__ data,    // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(UNE_WAVES * WAVE) void json_unescape_kernel(
     int32_t* __restrict__ out_flags)     // [B] UNE_* bits
 {
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * UNE_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform; the kernel has no barrier
     const int32_t rbeg = beg[r], rend = end_[r];
 
@@ -121,7 +117,7 @@ __global__ __launch_bounds__(UNE_WAVES * WAVE) void json_unescape_kernel(
         }
 
         // ---- leaders: backslashes at even offsets of their run ----
-        const uint64_t skipm = une_below(skip);
+        const uint64_t skipm = lanes_below(skip);
         bs &= ~skipm;
         const uint64_t follows = bs << 1;
         const uint64_t odd_starts = bs & ~UNE_EVEN & ~follows;
@@ -241,8 +237,8 @@ extern "C" int forge_json_unescape(
     if (batch <= 0) return 0;
     if (!out || !out_end || !out_flags) return FORGE_ERR_JSON_UNESCAPE;
     hipStream_t s = (hipStream_t)stream;
-    int grid = ceil_div(batch, UNE_WAVES);
-    hipLaunchKernelGGL(json_unescape_kernel, dim3(grid), dim3(UNE_WAVES * WAVE), 0, s,
+    int grid = ceil_div(batch, ROW_WAVES);
+    hipLaunchKernelGGL(json_unescape_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), 0, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (uint8_t*)out, (int32_t*)out_end, (int32_t*)out_flags);
     return (int)hipGetLastError();

@@ -55,7 +55,6 @@
 
 #include "common.h"
 
-#define UNI_WAVES 4                  // waves (= requests) per block
 #define UNI_INVALID 64u
 #define UNI_MIXED 128u
 #define UNI_TABLE_KINDS 6            // kind bits a table range may carry
@@ -69,8 +68,6 @@ static_assert(FORGE_UNICODE_SCAN_MAX_RANGES * FORGE_UNICODE_SCAN_RANGE_BYTES == 
 #define UNI_CYRILLIC 3u
 #define UNI_COMMON 4u
 
-// lanes [0, n) as a mask; 0 <= n <= 64
-__device__ __forceinline__ uint64_t uni_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 // the length of the run of set bits from lane 0 up
 __device__ __forceinline__ int uni_run_up(uint64_t m) { return ~m ? __builtin_ctzll(~m) : WAVE; }
 // the first lane of the run of set bits that ends in lane 63
@@ -106,7 +103,7 @@ __device__ __forceinline__ void uni_close(UniWord& w, int32_t end, uint32_t repo
     w.open = false;
 }
 
-__global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void unicode_scan_kernel(
     const uint8_t* __restrict__ data,    // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
     __syncthreads();
 
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * UNI_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform
     const int32_t rbeg = beg[r], rend = end_[r];
 
@@ -153,14 +150,14 @@ __global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
             // ASCII only and no word that could turn out mixed: only the word state moves
             if (w.open) {
                 const int n = (aword & 1ull) ? uni_run_up(aword) : 0;
-                w.lat = w.lat || (alet & uni_below(n));
+                w.lat = w.lat || (alet & lanes_below(n));
                 if (n < WAVE) w.open = false;   // a word with no other-script letter is no finding
             }
             if ((aword >> (WAVE - 1)) && !w.open) {
                 const int s = uni_tail_start(aword);
                 w.beg = p0 + s;
                 w.open = true;
-                w.lat = alet & ~uni_below(s);
+                w.lat = alet & ~lanes_below(s);
                 w.oth = false;
             }
             continue;
@@ -240,7 +237,7 @@ __global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
         uint64_t done = 0;
         if (w.open) {
             const int n = (wbytes & 1ull) ? uni_run_up(wbytes) : 0;
-            done = uni_below(n);
+            done = lanes_below(n);
             w.lat = w.lat || (lat & done);
             w.oth = w.oth || (oth & done);
             if (n < WAVE) uni_close(w, p0 + n, report_mask, o);
@@ -249,11 +246,11 @@ __global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
         uint64_t rem = oth & ~done;
         while (rem) {
             const int at = __builtin_ctzll(rem);
-            const uint64_t gaps = ~wbytes & uni_below(at);
+            const uint64_t gaps = ~wbytes & lanes_below(at);
             const int s = gaps ? WAVE - __builtin_clzll(gaps) : 0;
             const uint64_t tail = ~(wbytes >> at);   // bit i: lane at + i is no word byte (or is past lane 63)
             const int e = tail ? at + __builtin_ctzll(tail) : WAVE;   // exclusive
-            const uint64_t seg = uni_below(e) & ~uni_below(s);
+            const uint64_t seg = lanes_below(e) & ~lanes_below(s);
             rem &= ~seg;
             if (e < WAVE && (lat & seg)) {
                 ++o.cnt[7];
@@ -264,8 +261,8 @@ __global__ __launch_bounds__(UNI_WAVES * WAVE) void unicode_scan_kernel(
             const int s = uni_tail_start(wbytes);
             w.beg = p0 + s;
             w.open = true;
-            w.lat = lat & ~uni_below(s);
-            w.oth = oth & ~uni_below(s);
+            w.lat = lat & ~lanes_below(s);
+            w.oth = oth & ~lanes_below(s);
         }
     }
     // a word that reaches the span end closes there
@@ -294,11 +291,11 @@ extern "C" int forge_unicode_scan(
     if (report_mask & ~FORGE_UNICODE_SCAN_ALL_KINDS) return FORGE_ERR_UNICODE_SCAN;
     if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int grid = ceil_div(batch, UNI_WAVES);
+    int grid = ceil_div(batch, ROW_WAVES);
     int trips = 0;
     while ((1 << trips) < n_ranges + 1) ++trips;
     size_t lds = (size_t)n_ranges * FORGE_UNICODE_SCAN_RANGE_BYTES;
-    hipLaunchKernelGGL(unicode_scan_kernel, dim3(grid), dim3(UNI_WAVES * WAVE), lds, s,
+    hipLaunchKernelGGL(unicode_scan_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), lds, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (const uint4*)table, n_ranges, trips, (uint32_t)report_mask,
                        (int32_t*)out_counts, (int32_t*)out_kinds, (int32_t*)out_first, (int32_t*)out_flags);

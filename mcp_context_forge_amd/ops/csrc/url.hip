@@ -46,7 +46,6 @@
 
 #include "common.h"
 
-#define URL_WAVES 4            // waves (= requests) per block
 #define URL_WIN FORGE_URL_SCAN_AUTH_MAX   // window bytes per wave
 #define URL_POWERS FORGE_URL_SCAN_AUTH_MAX
 #define URL_SCHEME_MAX 16
@@ -69,12 +68,9 @@ struct UrlSlot {
 };
 static_assert(sizeof(UrlSlot) == 16 && offsetof(UrlSlot, key) == 0 && offsetof(UrlSlot, tag) == 4 &&
               offsetof(UrlSlot, off) == 8 && offsetof(UrlSlot, len) == 12, "UrlSlot is u32[4] in ops/url.py");
-static_assert(FORGE_URL_SCAN_LDS_SLOTS * sizeof(UrlSlot) + 2 * URL_POWERS * 4 + URL_WAVES * URL_WIN <= 32 * 1024,
+static_assert(FORGE_URL_SCAN_LDS_SLOTS * sizeof(UrlSlot) + 2 * URL_POWERS * 4 + ROW_WAVES * URL_WIN <= 32 * 1024,
               "slots, powers and windows share 32 KiB of LDS");
 static_assert(URL_WIN == 4 * WAVE, "the authority is read in four steps");
-
-// lanes [0, n) as a mask; 0 <= n <= 64
-__device__ __forceinline__ uint64_t url_below(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 
 __device__ __forceinline__ bool url_scheme_char(uint32_t b) {
     const uint32_t l = b | 0x20u;
@@ -104,7 +100,7 @@ __device__ __forceinline__ uint32_t url_suffix_sum(uint32_t v, int lane) {
     return v;
 }
 
-__global__ __launch_bounds__(URL_WAVES * WAVE) void url_scan_kernel(
+__global__ __launch_bounds__(ROW_WAVES * WAVE) void url_scan_kernel(
     const uint8_t* __restrict__ data,    // packed bytes
     const int32_t* __restrict__ beg,
     const int32_t* __restrict__ end_,
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(URL_WAVES * WAVE) void url_scan_kernel(
     extern __shared__ __align__(16) uint8_t lds_raw[];
     uint32_t* lpow = (uint32_t*)lds_raw;
     uint8_t* win = lds_raw + 2 * URL_POWERS * 4 + (threadIdx.x / WAVE) * URL_WIN;
-    UrlSlot* lslots = (UrlSlot*)(lds_raw + 2 * URL_POWERS * 4 + URL_WAVES * URL_WIN);
+    UrlSlot* lslots = (UrlSlot*)(lds_raw + 2 * URL_POWERS * 4 + ROW_WAVES * URL_WIN);
     for (int i = threadIdx.x; i < 2 * URL_POWERS; i += blockDim.x) lpow[i] = powers[i];
     if (slots_in_lds)
         for (int i = threadIdx.x; i < n_slots; i += blockDim.x) lslots[i] = slots[i];
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(URL_WAVES * WAVE) void url_scan_kernel(
     __syncthreads();
 
     const int lane = threadIdx.x & (WAVE - 1);
-    const int r = blockIdx.x * URL_WAVES + (threadIdx.x / WAVE);
+    const int r = blockIdx.x * ROW_WAVES + (threadIdx.x / WAVE);
     if (r >= batch) return;  // wave-uniform
     const int32_t rbeg = beg[r], rend = end_[r];
     const uint32_t slot_mask = (uint32_t)n_slots - 1u;
@@ -185,14 +181,14 @@ __global__ __launch_bounds__(URL_WAVES * WAVE) void url_scan_kernel(
                 if (tb) {
                     const int t = __builtin_ctzll(tb);
                     e = k * WAVE + t;
-                    before = url_below(t);
+                    before = lanes_below(t);
                 }
                 const uint64_t atb = __ballot(c == '@') & before;
                 uint64_t colb = __ballot(c == ':') & before;
                 if (atb) {
                     const int t = WAVE - 1 - __builtin_clzll(atb);
                     last_at = k * WAVE + t;
-                    colb &= ~url_below(t + 1);
+                    colb &= ~lanes_below(t + 1);
                     first_colon = -1;
                 }
                 if (first_colon < 0 && colb) first_colon = k * WAVE + __builtin_ctzll(colb);
@@ -336,9 +332,9 @@ extern "C" int forge_url_scan(
     if (batch <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int in_lds = n_slots <= FORGE_URL_SCAN_LDS_SLOTS ? 1 : 0;
-    int grid = ceil_div(batch, URL_WAVES);
-    size_t lds = 2 * URL_POWERS * 4 + URL_WAVES * URL_WIN + (in_lds ? (size_t)n_slots * sizeof(UrlSlot) : 0);
-    hipLaunchKernelGGL(url_scan_kernel, dim3(grid), dim3(URL_WAVES * WAVE), lds, s,
+    int grid = ceil_div(batch, ROW_WAVES);
+    size_t lds = 2 * URL_POWERS * 4 + ROW_WAVES * URL_WIN + (in_lds ? (size_t)n_slots * sizeof(UrlSlot) : 0);
+    hipLaunchKernelGGL(url_scan_kernel, dim3(grid), dim3(ROW_WAVES * WAVE), lds, s,
                        (const uint8_t*)data, (const int32_t*)beg, (const int32_t*)end_, batch,
                        (const UrlSlot*)slots, n_slots, in_lds, (const uint8_t*)pool, (const uint32_t*)powers,
                        (uint32_t)report_mask,

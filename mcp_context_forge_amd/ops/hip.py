@@ -250,6 +250,15 @@ def token_entropy(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, sym_
     return max_h, span, n_runs, flags
 
 
+def _scan_outputs(batch: int, k: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The four outputs of a wave-per-request scan: (counts i32[B, k], mask
+    i32[B], first i32[B, 2], flags i32[B]), uninitialised."""
+    return (torch.empty((batch, k), dtype=torch.int32, device=device),
+            torch.empty(batch, dtype=torch.int32, device=device),
+            torch.empty((batch, 2), dtype=torch.int32, device=device),
+            torch.empty(batch, dtype=torch.int32, device=device))
+
+
 # Same value as FORGE_DECODE_SCAN_TABLE_LIMIT in csrc/forge_api.h: the keyword
 # tables of decode_scan (scan_table_bytes of them) always live in LDS.
 DECODE_SCAN_TABLE_LIMIT = exfil.KW_TABLE_LIMIT
@@ -274,11 +283,7 @@ def decode_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, sym_ta
     if sym_table.dtype != torch.uint8 or sym_table.numel() != 256:
         raise ValueError("symbol table must be uint8[256]")
     if out is None:
-        dev = data.device
-        out = (torch.empty((batch, 3), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev))
+        out = _scan_outputs(batch, 3, data.device)
     counts, kw, span, flags = out
     _check("forge_decode_scan", _load().forge_decode_scan(
         _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(sym_table), int(bits), int(min_len),
@@ -312,11 +317,7 @@ def sql_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, kw_tables
     if kw_len.dtype != torch.int32:
         raise ValueError("kw_len must be int32")
     if out is None:
-        dev = data.device
-        out = (torch.empty((batch, 4), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev))
+        out = _scan_outputs(batch, 4, data.device)
     counts, blocked, first, flags = out
     _check("forge_sql_scan", _load().forge_sql_scan(
         _ptr(data), _ptr(beg), _ptr(end), batch,
@@ -357,11 +358,7 @@ def url_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table: De
     call graph-capture safe."""
     batch = beg.numel()
     if out is None:
-        dev = data.device
-        out = (torch.empty((batch, 4), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev))
+        out = _scan_outputs(batch, 4, data.device)
     counts, mask, first, flags = out
     _check("forge_url_scan", _load().forge_url_scan(
         _ptr(data), _ptr(beg), _ptr(end), batch,
@@ -393,11 +390,7 @@ def account_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table
     call graph-capture safe."""
     batch = beg.numel()
     if out is None:
-        dev = data.device
-        out = (torch.empty((batch, 4), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev))
+        out = _scan_outputs(batch, 4, data.device)
     counts, kinds, first, flags = out
     _check("forge_account_scan", _load().forge_account_scan(
         _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(table.lengths), int(report_mask),
@@ -436,11 +429,7 @@ def unicode_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table
     call graph-capture safe."""
     batch = beg.numel()
     if out is None:
-        dev = data.device
-        out = (torch.empty((batch, UNICODE_SCAN_KINDS), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.empty(batch, dtype=torch.int32, device=dev))
+        out = _scan_outputs(batch, UNICODE_SCAN_KINDS, data.device)
     counts, kinds, first, flags = out
     _check("forge_unicode_scan", _load().forge_unicode_scan(
         _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(table.ranges), table.n_ranges, int(report_mask),

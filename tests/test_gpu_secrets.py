@@ -336,12 +336,12 @@ def test_pipeline_noop_without_the_plugin(monkeypatch):
     async def run():
         gpu = await _build(gpu=True, with_secrets=False)
         pipe = gpu.gpu_pipeline
-        assert pipe.secrets is None and "secrets" not in pipe.banks and pipe._secret_tabs == []
+        assert pipe.secrets is None and "secrets" not in pipe.banks and "secrets" not in pipe.prefilters
         out = await gpu.process_rpc_batch([r for r, _ in _traffic()])
         assert all(b'"result"' in o for o in out)
         st = pipe.stats()
         assert st["secrets_routed"] == 0 and "gp0_secrets" not in st["timing_s"]
-        assert "secrets" not in pipe._bankset3.index and pipe._tools.secrets is None
+        assert "secrets" not in pipe._bankset3.index and "secrets" not in pipe._tools.prefilter
         await gpu.shutdown()
 
     asyncio.run(run())

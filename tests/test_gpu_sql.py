@@ -493,7 +493,7 @@ def test_pipeline_sql_off_launches_nothing():
         out = await e.process_rpc_batch([_mk_raw("fast-time-echo", _j({"q": "DROP TABLE users"}), 1)])
         assert "result" in json.loads(out[0])
         st = e.gpu_pipeline.stats()
-        assert st["sql_routed"] == 0 and st["fast_path"] == 1 and e.gpu_pipeline._tools.sql is None
+        assert st["sql_routed"] == 0 and st["fast_path"] == 1 and "sql" not in e.gpu_pipeline._tools.prefilter
         await e.shutdown()
 
     asyncio.run(run())

