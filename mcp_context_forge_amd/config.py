@@ -143,6 +143,10 @@ class Settings(BaseModel):
     gpu_semcache_threshold: float = 0.92
     # two-stage lookup: random-projection sketch dim (0 = full sweep)
     gpu_semcache_sketch_dim: int = 256
+    # identity-aware top-k lookup (semcache.hip): the sweep ranks only the
+    # caller's own, unexpired entries and verifies this many candidates per
+    # row; 0 = the single-candidate lookup. Needs a sketch of 64..512 dimensions
+    gpu_semcache_topk: int = Field(default=0, ge=0, le=8)
     gpu_streams: int = 2              # compute + copy overlap
     gpu_dtype: str = "bf16"
     # decode JSON string escapes on the GPU (unescape.hip) ahead of the raw-byte

@@ -216,6 +216,7 @@ class GpuPluginPipeline:
                 ttl_s=self.semcache_plugin.ttl,
                 device=device,
                 sketch_dim=s.gpu_semcache_sketch_dim,
+                topk=s.gpu_semcache_topk,
             )
 
         # native rewrite lane (rewrite.cpp): fixed-index PII maps for the
@@ -500,6 +501,8 @@ class GpuPluginPipeline:
     async def _gpu_rows(self, rs: RowSet) -> None:
         """Pass 1 → native decide → answers, rewrites and dispatch."""
         tools, blob, tool_idx, m = rs.tools, rs.blob, rs.tool_idx, len(rs)
+        # semcache identity = tool_hash XOR user_hash (tenant-scoped)
+        th_arr = np.where(tool_idx >= 0, tools.thash[np.clip(tool_idx, 0, None)] ^ rs.uh, 0)
 
         # --- GPU pass 1 over raw argument spans ---
         def pass1_extra(data_gpu, beg_t, end_t):
@@ -510,7 +513,7 @@ class GpuPluginPipeline:
             if self.classifier is not None:
                 scores_t = self.classifier.forward(feats)[:m]
             if self.semcache is not None:
-                bv, bi, feats_sk = self.semcache.lookup(feats)
+                bv, bi, feats_sk = self.semcache.lookup(feats, idents=th_arr)
                 cache_val_t, cache_idx_t = bv[:m], bi[:m]
             return feats, scores_t, cache_val_t, cache_idx_t, feats_sk
 
@@ -549,8 +552,6 @@ class GpuPluginPipeline:
             mod_cat = np.ascontiguousarray(sc_np.argmax(axis=1).astype(np.int32))
             mod_block = (mod_score >= self.moderation.threshold).astype(np.uint8)
 
-        # semcache identity = tool_hash XOR user_hash (tenant-scoped)
-        th_arr = np.where(tool_idx >= 0, tools.thash[np.clip(tool_idx, 0, None)] ^ rs.uh, 0)
         hit = np.zeros(m, dtype=np.uint8)
         hit_slot = np.full(m, -1, dtype=np.int32)
         if cache_val_t is not None:

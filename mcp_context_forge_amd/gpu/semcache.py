@@ -10,6 +10,7 @@ indexed by slot.
 
 from __future__ import annotations
 
+import logging
 import time
 from typing import Any, List, Optional, Tuple
 
@@ -17,6 +18,9 @@ import numpy as np
 import torch
 
 from ..ops import hip
+from ..ops.semcache import stamp_of
+
+log = logging.getLogger(__name__)
 
 
 def tool_hash(name: str) -> int:
@@ -29,8 +33,9 @@ def tool_hash(name: str) -> int:
 class GpuSemanticCache:
     def __init__(self, capacity: int = 65536, dim: int = 4096, threshold: float = 0.92,
                  ttl_s: float = 600.0, device: str = "cuda", chunk: int = 4096,
-                 sketch_dim: int = 256):
+                 sketch_dim: int = 256, topk: int = 0):
         assert capacity % 128 == 0 and chunk % 128 == 0 and dim % 64 == 0
+        assert 0 <= topk <= hip.SKETCH_TOPK_MAX_K
         self.capacity = capacity
         self.dim = dim
         self.threshold = threshold
@@ -54,6 +59,18 @@ class GpuSemanticCache:
         else:
             self.proj_t = None
             self.keys_sk = None
+        # identity-aware top-k lookup (semcache.hip): per-slot identity and
+        # insert time on the device, so that the sweep itself skips other
+        # tenants' and expired entries and keeps `topk` candidates per row
+        self.topk = topk if (topk and 64 <= self.sketch_dim <= 512) else 0
+        if topk and not self.topk:
+            log.warning("gpu semcache: topk=%d needs a sketch of 64..512 dimensions (sketch_dim=%s); "
+                        "using the single-candidate lookup", topk, sketch_dim)
+        self.t0 = time.monotonic()
+        self.ident = self.stamp = None
+        if self.topk:
+            self.ident = torch.zeros(capacity, dtype=torch.int64, device=device)
+            self.stamp = torch.zeros(capacity, dtype=torch.int32, device=device)
 
         # host-side metadata mirrors (slot-indexed)
         self.tool_hashes = np.zeros(capacity, dtype=np.int64)
@@ -64,12 +81,27 @@ class GpuSemanticCache:
         self.hits = 0
         self.misses = 0
 
-    def lookup(self, feats_bf16: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    def min_stamp(self, now: float) -> int:
+        return stamp_of(now - self.ttl_s, self.t0)
+
+    def lookup(self, feats_bf16: torch.Tensor, idents: Optional[np.ndarray] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """feats [Bpad, dim] bf16 → (best_val fp32 [Bpad], best_idx i32 [Bpad]) on device.
 
         Chunked sweep over the key matrix; scores for padded/invalid slots are
         suppressed by the validity mask inside the merge kernel.
+
+        With topk >= 1 and `idents` (i64, one per leading row; the rest of
+        Bpad reads as identity 0): one fused sweep that only ranks the slots
+        of the row's identity whose stamp is not older than the TTL, keeps
+        topk of them and verifies them all in full dimension. The device
+        filter works on 1/16 s ticks rounded down, a superset of the host's
+        exact `now - ts <= ttl`: an entry expired by less than one tick can
+        at worst win here and is then refused by resolve_hits_np, which
+        still runs on the winner.
         """
+        if self.topk and idents is not None:
+            return self._lookup_topk(feats_bf16, idents)
         bpad = feats_bf16.shape[0]
         best_val = torch.full((bpad,), -1e30, dtype=torch.float32, device=self.device)
         best_idx = torch.full((bpad,), -1, dtype=torch.int32, device=self.device)
@@ -97,6 +129,21 @@ class GpuSemanticCache:
             nc = min(self.chunk, self.capacity - c0)
             scores = hip.gemm_bt(feats_bf16, self.keys[c0:c0 + nc])
             hip.rows_argmax_merge(scores, best_val, best_idx, idx_base=c0, valid=self.valid[c0:c0 + nc])
+        return best_val, best_idx, sk
+
+    def _lookup_topk(self, feats_bf16: torch.Tensor, idents: np.ndarray):
+        bpad = feats_bf16.shape[0]
+        sk = hip.gemm_bt(feats_bf16, self.proj_t, out_bf16=True)
+        if self.size == 0:
+            return (torch.full((bpad,), -1e30, dtype=torch.float32, device=self.device),
+                    torch.full((bpad,), -1, dtype=torch.int32, device=self.device), sk)
+        q_ident = np.zeros(bpad, dtype=np.int64)
+        q_ident[:len(idents)] = np.asarray(idents).astype(np.int64)
+        q_ident_t = torch.from_numpy(q_ident).to(self.device, non_blocking=True)
+        active = min(self.size, self.capacity)
+        _, cand = hip.sketch_topk(sk, self.keys_sk, self.ident, self.stamp, self.valid, q_ident_t,
+                                  self.min_stamp(time.monotonic()), active, self.topk)
+        best_val, best_idx = hip.verify_topk(feats_bf16, self.keys, cand)
         return best_val, best_idx, sk
 
     def resolve_hits_np(self, best_val: np.ndarray, best_idx: np.ndarray,
@@ -160,6 +207,11 @@ class GpuSemanticCache:
         now = time.monotonic()
         self.tool_hashes[slots] = tool_hashes
         self.timestamps[slots] = now
+        if self.topk:
+            slot_l = slot_t.long()
+            ident_t = torch.from_numpy(np.asarray(tool_hashes).astype(np.int64)).to(self.device, non_blocking=True)
+            self.ident[slot_l] = ident_t
+            self.stamp[slot_l] = stamp_of(now, self.t0)
 
     def insert_batch(self, feats_bf16: torch.Tensor, rows: List[int],
                      tool_hashes: List[int], results: List[Any]) -> None:
@@ -174,4 +226,4 @@ class GpuSemanticCache:
 
     def stats(self) -> dict:
         return {"size": self.size, "capacity": self.capacity, "hits": self.hits, "misses": self.misses,
-                "hbm_bytes": self.keys.numel() * 2}
+                "hbm_bytes": self.keys.numel() * 2, "topk": self.topk}

@@ -28,6 +28,7 @@
 #define FORGE_ERR_ACCOUNT_SCAN 9010   /* account_scan: report_mask */
 #define FORGE_ERR_UNICODE_SCAN 9011   /* unicode_scan: n_ranges or report_mask */
 #define FORGE_ERR_JSON_UNESCAPE 9012  /* json_unescape: a null output with batch > 0 */
+#define FORGE_ERR_SEMCACHE_TOPK 9013  /* sketch_topk / verify_topk: k, S, B, D, splits or a null output */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -90,6 +91,25 @@
 #define FORGE_UNICODE_SCAN_RANGE_BYTES 16
 #define FORGE_UNICODE_SCAN_KINDS 8
 #define FORGE_UNICODE_SCAN_ALL_KINDS 255
+
+/* forge_sketch_topk keeps 1..FORGE_SKETCH_TOPK_MAX_K candidates per row. Its
+ * grid is (B / 64) x splits; a split sweeps at most FORGE_SKETCH_TOPK_MAX_TILES
+ * tiles of 64 slots and there are at most FORGE_SKETCH_TOPK_MAX_SPLITS, so one
+ * launch covers 64 * 512 * 64 slots. With splits == 0 the launcher takes the
+ * fewest splits that give FORGE_SKETCH_TOPK_TARGET_BLOCKS workgroups (two per
+ * CU of a 256-CU part), at most one per slot tile and at most the cap. A
+ * workgroup uses FORGE_SKETCH_TOPK_LDS_BYTES(S) bytes of LDS: the query tile
+ * (128 * S) plus a 3-chunk key ring, one score tile, the slot metadata ring,
+ * the row identities and the live-tile list (47744): 80512 at S = 256, two
+ * workgroups per 160 KiB CU; 113280 at the cap S = 512. forge_verify_topk
+ * holds a feature row of up to FORGE_VERIFY_TOPK_MAX_D bf16 in registers.
+ * ops/hip.py carries MAX_K and MAX_SPLITS as SKETCH_TOPK_MAX_K / _MAX_SPLITS. */
+#define FORGE_SKETCH_TOPK_MAX_K 8
+#define FORGE_SKETCH_TOPK_MAX_SPLITS 64
+#define FORGE_SKETCH_TOPK_MAX_TILES 512
+#define FORGE_SKETCH_TOPK_TARGET_BLOCKS 512
+#define FORGE_SKETCH_TOPK_LDS_BYTES(S) ((S) * 128 + 47744)
+#define FORGE_VERIFY_TOPK_MAX_D 8192
 
 typedef void (*forge_task_fn)(int index, void* ctx);
 
@@ -230,6 +250,37 @@ int forge_rows_gather_scatter_bf16(const void* src, const void* src_rows, const 
 
 int forge_verify_dot(const void* feats, const void* keys, const void* idx, void* out,
                      int M, int D, void* stream);
+
+/* The fused sketch sweep of the semantic cache (semcache.hip): for each of the
+ * B rows of q_sk [B, S] bf16, the k best eligible slots of keys_sk in the
+ * order (score descending, slot ascending), padded with (-1e30, -1). Slot c
+ * is eligible for row r when c < active, valid[c] != 0, ident[c] ==
+ * q_ident[r] (i64) and stamp[c] >= min_stamp (u32). Scores have the bits of
+ * forge_gemm_bt and never reach global memory. keys_sk, ident, stamp and valid
+ * hold at least active rounded up to 64 slots; valid is 4-byte aligned. partial_val f32 / partial_idx
+ * i32 [B, splits, k] are scratch (FORGE_SKETCH_TOPK_MAX_SPLITS covers
+ * splits == 0); out_val f32 / out_idx i32 [B, k]; every element of out_* is
+ * written and does not depend on splits. active == 0 launches only the merge
+ * kernel, which writes the padding; B == 0 launches nothing. k outside
+ * 1..FORGE_SKETCH_TOPK_MAX_K, S no multiple of 64 in 64..512, B no multiple
+ * of 64, active < 0, splits outside 0..FORGE_SKETCH_TOPK_MAX_SPLITS or too few
+ * for active (FORGE_SKETCH_TOPK_MAX_TILES per split), a null out_* or, with
+ * active > 0, a null partial_* return FORGE_ERR_SEMCACHE_TOPK with nothing
+ * launched. */
+int forge_sketch_topk(const void* q_sk, const void* keys_sk, const void* ident, const void* stamp,
+                      const void* valid, const void* q_ident, uint32_t min_stamp, int active,
+                      int B, int S, int k, int splits,
+                      void* partial_val, void* partial_idx, void* out_val, void* out_idx,
+                      void* stream);
+
+/* One wave per row: the exact bf16 dot (the bits of forge_verify_dot) of
+ * feats[r] with keys[cand[r, j]] for every cand[r, j] >= 0, j < k; best_val
+ * f32[M] the greatest, best_idx i32[M] its slot, the first listed on a tie,
+ * (-1e30, -1) for a row without a candidate. Every element is written.
+ * D % 8 returns FORGE_ERR_ROW_ALIGN; k outside 1..FORGE_SKETCH_TOPK_MAX_K or
+ * D outside 8..FORGE_VERIFY_TOPK_MAX_D FORGE_ERR_SEMCACHE_TOPK. */
+int forge_verify_topk(const void* feats, const void* keys, const void* cand, int k, int M, int D,
+                      void* best_val, void* best_idx, void* stream);
 
 /* ---- native rescoring session (rescore.hip) ----
  * featurize + classifier + head over up to max_rows texts per submit, with

@@ -54,6 +54,8 @@ _API = {
     "forge_rows_argmax_merge": _sig("i", "p iii p pp p"),
     "forge_rows_gather_scatter_bf16": _sig("i", "ppp p p ii p"),
     "forge_verify_dot": _sig("i", "ppp p ii p"),
+    "forge_sketch_topk": _sig("i", "ppppp p u i iiii pp pp p"),
+    "forge_verify_topk": _sig("i", "ppp iii pp p"),
     "forge_rescore_new": _sig("p", "pppp iii i l i"),
     "forge_rescore_submit": _sig("i", "p ss i p"),
     "forge_rescore_poll": _sig("i", "p i"),
@@ -588,6 +590,66 @@ def verify_dot(feats: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor) -> to
     out = torch.empty(m, dtype=torch.float32, device=feats.device)
     _check("forge_verify_dot", _load().forge_verify_dot(
         _ptr(feats), _ptr(keys), _ptr(idx), _ptr(out), m, d, _stream()))
+    return out
+
+
+# Same values as FORGE_ERR_SEMCACHE_TOPK / FORGE_SKETCH_TOPK_MAX_K / _MAX_SPLITS in csrc/forge_api.h.
+ERR_SEMCACHE_TOPK = 9013
+SKETCH_TOPK_MAX_K = 8
+SKETCH_TOPK_MAX_SPLITS = 64
+
+
+def sketch_topk(q_sk: torch.Tensor, keys_sk: torch.Tensor, ident: torch.Tensor, stamp: torch.Tensor,
+                valid: torch.Tensor, q_ident: torch.Tensor, min_stamp: int, active: int, k: int,
+                splits: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best eligible slots of each sketch row in one fused sweep
+    (semcache.hip; oracle ops/semcache.py sketch_topk_reference): scores with
+    the bits of gemm_bt(q_sk, keys_sk), masked by slot < active, valid,
+    ident[slot] == q_ident[row] and stamp[slot] >= min_stamp (unsigned), kept
+    in the order (score descending, slot ascending) and never written to
+    global memory. q_sk bf16 [B, S] (B % 64 == 0, S % 64 == 0, 64..512),
+    keys_sk bf16 [C, S] with C % 64 == 0 and active <= C, ident i64[C], stamp
+    i32[C], valid u8[C], q_ident i64[B]. splits 0 lets the launcher choose.
+    → (val f32[B, k], idx i32[B, k]), padded with (-1e30, -1); `out` (those
+    two, preallocated) is written in place."""
+    assert q_sk.dtype == torch.bfloat16 and keys_sk.dtype == torch.bfloat16
+    assert ident.dtype == torch.int64 and q_ident.dtype == torch.int64
+    assert stamp.dtype == torch.int32 and valid.dtype == torch.uint8
+    assert all(t.is_contiguous() for t in (q_sk, keys_sk, ident, stamp, valid, q_ident))
+    b, s = q_sk.shape
+    c = keys_sk.shape[0]
+    assert keys_sk.shape[1] == s and c % 64 == 0 and active <= c and valid.data_ptr() % 4 == 0
+    assert ident.numel() == c and stamp.numel() == c and valid.numel() == c and q_ident.numel() == b
+    if out is None:
+        out = (torch.empty((b, k), dtype=torch.float32, device=q_sk.device),
+               torch.empty((b, k), dtype=torch.int32, device=q_sk.device))
+    n_part = b * (splits if 0 < splits <= SKETCH_TOPK_MAX_SPLITS else SKETCH_TOPK_MAX_SPLITS) * max(k, 1)
+    part_val = torch.empty(n_part, dtype=torch.float32, device=q_sk.device)
+    part_idx = torch.empty(n_part, dtype=torch.int32, device=q_sk.device)
+    _check("forge_sketch_topk", _load().forge_sketch_topk(
+        _ptr(q_sk), _ptr(keys_sk), _ptr(ident), _ptr(stamp), _ptr(valid), _ptr(q_ident),
+        int(min_stamp), int(active), b, s, int(k), int(splits),
+        _ptr(part_val), _ptr(part_idx), _ptr(out[0]), _ptr(out[1]), _stream()))
+    return out
+
+
+def verify_topk(feats: torch.Tensor, keys: torch.Tensor, cand: torch.Tensor,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact bf16 dot of feats[r] with keys[cand[r, j]] for every candidate
+    >= 0, the bits verify_dot gives for the pair (semcache.hip; oracle
+    ops/semcache.py verify_topk_reference). cand i32 [M, k], k in 1..8.
+    → (best_val f32[M], best_idx i32[M]): the greatest dot and its slot, the
+    first listed on a tie, (-1e30, -1) without a candidate."""
+    assert feats.dtype == torch.bfloat16 and keys.dtype == torch.bfloat16 and cand.dtype == torch.int32
+    assert feats.is_contiguous() and keys.is_contiguous() and cand.is_contiguous()
+    m, d = feats.shape
+    assert cand.shape[0] == m and keys.shape[1] == d
+    if out is None:
+        out = (torch.empty(m, dtype=torch.float32, device=feats.device),
+               torch.empty(m, dtype=torch.int32, device=feats.device))
+    _check("forge_verify_topk", _load().forge_verify_topk(
+        _ptr(feats), _ptr(keys), _ptr(cand), cand.shape[1], m, d, _ptr(out[0]), _ptr(out[1]), _stream()))
     return out
 
 
