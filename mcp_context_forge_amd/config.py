@@ -153,6 +153,11 @@ class Settings(BaseModel):
     # prefilters, so rows with \n, \t, \\u.... stay on the GPU lane; off: such rows
     # run the CPU chain
     gpu_unescape: bool = False
+    # check the argument schemas the byte patterns cannot hold (enum, bounds,
+    # lengths, additionalProperties: false, type lists) with a JSON structure
+    # walk on the GPU (schema.hip); rows it passes skip the host validator. off:
+    # every such row is validated on the host
+    gpu_schema_kernel: bool = False
 
     # --- native HTTP edge (C++ epoll owner loop, transports/native_edge.py) ---
     native_edge_port: int = 0         # 0 = disabled

@@ -15,7 +15,7 @@ from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from ..ops import dfa, hip
+from ..ops import dfa, hip, schema
 from ..plugins.framework import HookType, PluginContext, PluginMode
 from .prefilters import PREFILTERS
 from .semcache import tool_hash
@@ -100,7 +100,7 @@ def pack_strtable(items: Iterable[Any]) -> Tuple[np.ndarray, np.ndarray]:
 class _ToolMeta:
     __slots__ = ("tool", "name", "tid", "itype", "thash", "native_kind", "native_client",
                  "client", "handler", "schema_mode", "required_bits", "typed_pairs",
-                 "has_output_schema", "original_name", "reachable", "host_chain", "a2a_fast")
+                 "has_output_schema", "original_name", "reachable", "host_chain", "a2a_fast", "schema_kernel")
 
     def __init__(self):
         self.schema_mode = "host"   # "trivial" | "fast" | "host"
@@ -111,13 +111,14 @@ class _ToolMeta:
         self.has_output_schema = False
         self.host_chain = False     # per-tool plugin binding forces the CPU chain
         self.a2a_fast = False       # in-proc agent, hooks fully GPU-covered
+        self.schema_kernel = False  # a "host" schema that schema.hip judges first (gpu_schema_kernel)
 
 
 class ToolTable:
     """One registry/plugin generation's tables. Arrays are indexed by the
     `tool_idx` that `toolmap` resolves; with no tools they hold one dummy
-    entry. `hostbound`, `sk_tables`, `schema_bank` and `graphs` are None where
-    absent. `prefilter` maps a handle of prefilters.PREFILTERS to bool[n_tools],
+    entry. `hostbound`, `sk_tables`, `schema_bank`, `schema_table` and `graphs`
+    are None where absent. `prefilter` maps a handle of prefilters.PREFILTERS to bool[n_tools],
     the tools that plugin is active for; a handle with no such tool is absent."""
 
     __slots__ = ("generation", "plugins_ver", "metas", "by_name", "index", "names", "tids",
@@ -126,7 +127,7 @@ class ToolTable:
                  "outschema", "thash", "semallow",
                  "flags", "postlane", "hostbound", "prefilter",
                  "rw_norm", "rw_regex", "rw_deny", "rw_pii", "rw_harm", "mod_app",
-                 "sk_tables", "sk_range")
+                 "sk_tables", "sk_range", "schema_table")
 
 
 # ---- per-tool meta ----
@@ -414,8 +415,20 @@ def schema_key_tables(t: ToolTable, metas: List[_ToolMeta]) -> None:
                        np.asarray(sk_ty, dtype=np.int8), np.asarray(sk_rq, dtype=np.uint8))
 
 
+def schema_kernel_table(metas: List[_ToolMeta], device):
+    """gpu_schema_kernel: the "host" schemas that compile for schema.hip, as one
+    device table indexed like the tool tables → hip.DeviceSchemaTable, or None
+    when none compiles. Those tools keep schema_mode "host" and are marked
+    `schema_kernel`; a row the kernel does not pass is validated as before."""
+    table = schema.compile_schemas([(m.tool.get("input_schema") or {}) if m.schema_mode == "host" else None
+                                    for m in metas])
+    for m, ok in zip(metas, table.compiled):
+        m.schema_kernel = ok
+    return hip.DeviceSchemaTable(table, device) if any(table.compiled) else None
+
+
 def build_tool_table(engine, h: PluginHandles, banks: Dict[str, Any], device, *,
-                     semcache_on: bool, harm_lane_ok: bool) -> ToolTable:
+                     semcache_on: bool, harm_lane_ok: bool, schema_kernel: bool = False) -> ToolTable:
     """The snapshot for the engine's current registry generation and plugins
     version. The owning pipeline attaches `graphs`, a new pass-1 GraphCache
     per table: captured graphs bake this table's bank pointers."""
@@ -430,6 +443,7 @@ def build_tool_table(engine, h: PluginHandles, banks: Dict[str, Any], device, *,
         b1.append(("schema", t.schema_bank))
     t.bankset1 = hip.ScanBankSet(b1, device)
     t.graphs = None
+    t.schema_table = schema_kernel_table(metas, device) if schema_kernel and h.schema_guard is not None else None
     flat_arrays(t, metas)
     tool_flags(t, metas, engine.plugins, h, banks.keys(), semcache_on, harm_lane_ok)
     schema_key_tables(t, metas)

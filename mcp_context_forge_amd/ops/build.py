@@ -18,7 +18,7 @@ LIB = Path(__file__).parent / "libforge_hip.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["scan.hip", "entropy.hip", "exfil.hip", "sql.hip", "url.hip", "account.hip", "unicode.hip", "unescape.hip", "featurize.hip", "json_guard.hip", "gemm_bf16.hip",
+SOURCES = ["scan.hip", "entropy.hip", "exfil.hip", "sql.hip", "url.hip", "account.hip", "unicode.hip", "unescape.hip", "schema.hip", "featurize.hip", "json_guard.hip", "gemm_bf16.hip",
            "runtime.hip", "gemm_v2.hip", "gemm_skinny.hip", "semcache.hip", "rescore.hip", "envelope.cpp", "upstream.cpp", "fastpath.cpp", "rewrite.cpp", "pool.cpp"]
 
 

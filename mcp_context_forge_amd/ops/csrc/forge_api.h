@@ -29,6 +29,7 @@
 #define FORGE_ERR_UNICODE_SCAN 9011   /* unicode_scan: n_ranges or report_mask */
 #define FORGE_ERR_JSON_UNESCAPE 9012  /* json_unescape: a null output with batch > 0 */
 #define FORGE_ERR_SEMCACHE_TOPK 9013  /* sketch_topk / verify_topk: k, S, B, D, splits or a null output */
+#define FORGE_ERR_SCHEMA_CHECK 9014   /* schema_check: a table count or a null output with batch > 0 */
 
 /* forge_scan* stage a bank's tables into LDS when they fit this many bytes;
  * ops/hip.py carries the same pair as SCAN_LDS_LIMIT / scan_table_bytes(). */
@@ -91,6 +92,25 @@
 #define FORGE_UNICODE_SCAN_RANGE_BYTES 16
 #define FORGE_UNICODE_SCAN_KINDS 8
 #define FORGE_UNICODE_SCAN_ALL_KINDS 255
+
+/* forge_schema_check walks tables of FORGE_SCHEMA_TOOL_BYTES, _PROP_BYTES and
+ * _ENUM_BYTES records (ops/schema.py lays them out and validates them before
+ * upload). A tool has at most FORGE_SCHEMA_MAX_TOOL_PROPS properties, one per
+ * lane. Tables of up to FORGE_SCHEMA_LDS_TOOLS tools and FORGE_SCHEMA_LDS_PROPS
+ * properties are staged into LDS once per block, larger ones are read from
+ * global memory. Counts outside 0..FORGE_SCHEMA_MAX_TOOLS / _PROPS / _ENUMS or a
+ * pool over FORGE_SCHEMA_POOL_MAX bytes are an argument error. ops/schema.py
+ * has them all. */
+#define FORGE_SCHEMA_TOOL_BYTES 24
+#define FORGE_SCHEMA_PROP_BYTES 40
+#define FORGE_SCHEMA_ENUM_BYTES 16
+#define FORGE_SCHEMA_MAX_TOOL_PROPS 64
+#define FORGE_SCHEMA_LDS_TOOLS 64
+#define FORGE_SCHEMA_LDS_PROPS 256
+#define FORGE_SCHEMA_MAX_TOOLS 4096
+#define FORGE_SCHEMA_MAX_PROPS (1 << 18)
+#define FORGE_SCHEMA_MAX_ENUMS (1 << 20)
+#define FORGE_SCHEMA_POOL_MAX ((int64_t)1 << 24)
 
 /* forge_sketch_topk keeps 1..FORGE_SKETCH_TOPK_MAX_K candidates per row. Its
  * grid is (B / 64) x splits; a split sweeps at most FORGE_SKETCH_TOPK_MAX_TILES
@@ -206,6 +226,23 @@ int forge_account_scan(const void* data, const void* beg, const void* end_, int 
 int forge_unicode_scan(const void* data, const void* beg, const void* end_, int batch,
                        const void* table, int n_ranges, int report_mask,
                        void* out_counts, void* out_kinds, void* out_first, void* out_flags,
+                       void* stream);
+
+/* One wave per request: walk the JSON structure of data[beg[r], end_[r])
+ * against the compiled schema of tool tool_idx[r] i32[batch] (schema.hip;
+ * ops/schema.py schema_check_reference is the definition). tools, props,
+ * enums, pool: the tables of ops/schema.py compile_schemas in device memory.
+ * Writes every element of out_verdict i32[batch] (0 PASS, 1 FAIL, 2 PUNT),
+ * out_fail i32[batch] (bit 0 missing required, 1 type, 2 enum, 3 bound,
+ * 4 length, 5 additional), out_punt i32[batch] (bit 0 backslash, 1 non-ASCII,
+ * 2 not an object, 3 long, 4 duplicate key, 5 number form, 6 no table) and
+ * out_seen u64[batch] (the tool's properties met); with a punt, fail and seen
+ * are 0. PASS implies that utils/jsonschema.validate accepts the decoded
+ * span. An empty batch launches nothing. */
+int forge_schema_check(const void* data, const void* beg, const void* end_, const void* tool_idx, int batch,
+                       const void* tools, int n_tools, const void* props, int n_props,
+                       const void* enums, int n_enums, const void* pool, int64_t pool_bytes,
+                       void* out_verdict, void* out_fail, void* out_punt, void* out_seen,
                        void* stream);
 
 /* One wave per request: the JSON string escapes of data[beg, end) decoded into

@@ -16,7 +16,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import account, entropy, exfil, sql, unicode, url
+from . import account, entropy, exfil, schema, sql, unicode, url
 from .dfa import ScanTables
 
 
@@ -44,6 +44,7 @@ _API = {
     "forge_url_scan": _sig("i", "ppp i pi pl p i pppp p"),
     "forge_account_scan": _sig("i", "ppp i pi pppp p"),
     "forge_unicode_scan": _sig("i", "ppp i pii pppp p"),
+    "forge_schema_check": _sig("i", "pppp i pi pi pi pl pppp p"),
     "forge_json_unescape": _sig("i", "ppp i ppp p"),
     "forge_featurize": _sig("i", "ppp ii pp p"),
     "forge_json_guard": _sig("i", "ppp i ii pp p"),
@@ -437,6 +438,55 @@ def unicode_scan(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, table
         _ptr(data), _ptr(beg), _ptr(end), batch, _ptr(table.ranges), table.n_ranges, int(report_mask),
         _ptr(counts), _ptr(kinds), _ptr(first), _ptr(flags), _stream()))
     return counts, kinds, first, flags
+
+
+# Same values as FORGE_ERR_SCHEMA_CHECK / FORGE_SCHEMA_LDS_TOOLS / _LDS_PROPS in csrc/forge_api.h.
+ERR_SCHEMA_CHECK = 9014
+SCHEMA_LDS_TOOLS = schema.LDS_TOOLS
+SCHEMA_LDS_PROPS = schema.LDS_PROPS
+
+
+class DeviceSchemaTable:
+    """A schema.SchemaTable (schema.compile_schemas) in device memory, validated
+    on the host first: the kernel indexes the property, enum and pool ranges
+    the records name without a check of its own."""
+
+    def __init__(self, table: "schema.SchemaTable", device: str = "cuda"):
+        schema.validate_table(table)   # raises on a table the kernel may not walk
+        self.meta = table
+
+        def up(b: bytes) -> torch.Tensor:   # 8 spare bytes: an empty part still has a pointer
+            return torch.from_numpy(np.frombuffer(b + bytes(8), dtype=np.uint8).copy()).to(device)
+
+        self.tools, self.props, self.enums, self.pool = up(table.tools), up(table.props), up(table.enums), up(table.pool)
+        self.in_lds = table.in_lds
+
+
+def schema_check(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor, tool_idx: torch.Tensor,
+                 table: DeviceSchemaTable, out: Optional[Tuple[torch.Tensor, ...]] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Walk each span's JSON structure against the compiled schema of its tool,
+    one wave per request (schema.hip; oracle ops/schema.py
+    schema_check_reference). tool_idx i32[B] indexes the table's tools; -1 or
+    an uncompiled tool gives NO_TABLE.
+    → (verdict i32[B] (schema.PASS / FAIL / PUNT), fail i32[B], punt i32[B],
+    seen i64[B] (the bits of a uint64)). The kernel writes every element;
+    `out` (those four, preallocated) makes the call graph-capture safe."""
+    batch = beg.numel()
+    if tool_idx.dtype != torch.int32 or tool_idx.numel() != batch:
+        raise ValueError("tool_idx must be int32, one per span")
+    if out is None:
+        dev = data.device
+        out = tuple(torch.empty(batch, dtype=dt, device=dev)
+                    for dt in (torch.int32, torch.int32, torch.int32, torch.int64))
+    verdict, fail, punt, seen = out
+    m = table.meta
+    _check("forge_schema_check", _load().forge_schema_check(
+        _ptr(data), _ptr(beg), _ptr(end), _ptr(tool_idx), batch,
+        _ptr(table.tools), m.n_tools, _ptr(table.props), m.n_props, _ptr(table.enums), m.n_enums,
+        _ptr(table.pool), len(m.pool),
+        _ptr(verdict), _ptr(fail), _ptr(punt), _ptr(seen), _stream()))
+    return verdict, fail, punt, seen
 
 
 def json_unescape(data: torch.Tensor, beg: torch.Tensor, end: torch.Tensor,
